@@ -6,9 +6,14 @@ One "step" = one complete edit group of BASELINE.json configs[1]: SD-v1.4-shaped
 null_text-form LocalBlend, CFG 7.5 (U-Net batch 8), 50 DDIM steps, cross_replace 0.8,
 self_replace 0.4 -- every attention call is one fused HIP kernel (edits + store in it).
 Text encoding is replaced by a synthetic context, no VAE decode.  By default each batch's 50
-DDIM steps replay HIP graphs captured once (pipeline.GraphedEditRunner, during the warm-up);
-the per-launch kernel timing (roofline, clock, attention totals) comes from an eager pass of the
-same batches right after the timed region (--eager: time the eager loop itself).
+DDIM steps replay HIP graphs captured once (pipeline.GraphedEditRunner, during the warm-up;
+--eager: time the eager loop itself).
+
+A plain run sets up, warms up, times --steps steps, writes the last step's results if
+--dump-outputs is given and prints the headline line.  --full adds everything else, as further
+fields of the same line: the per-launch kernel timing (roofline, shader clock, attention totals,
+HBM-bound launches) from an eager pass of the same batches right after the timed region, and the
+CPU baseline.
 
 Multi-GPU: one process per GPU (torchrun); edit groups (seeds) are partitioned across ranks
 (weak scaling, no data-path collective); the final latents are all-gathered over RCCL once
@@ -21,6 +26,7 @@ import subprocess
 import sys
 import time
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "prompt-to-prompt_amd"))
 sys.path.insert(0, ROOT)
@@ -441,6 +447,26 @@ def cpu_baseline(num_ddim_steps: int, sample_steps: int = 2):
                       f"reference itself is not importable here (no diffusers)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rows, arrays):
+    """--dump-outputs: rows `rows` (the groups of the last timed step) of every result the timed
+    sweep returned, one float32 DIR/<name>.npy each.  The inputs are seeded (weights, x_T, text
+    context), so two builds given the same arguments write comparable arrays.  Together the files
+    stay under DUMP_LIMIT_BYTES: a larger result keeps a fixed, seeded sample of its elements
+    (flattened, in index order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // len(arrays) - 4096     # (per file, its header included)
+    for name, t in arrays.items():
+        a = t[rows].detach().to("cpu", torch.float32).contiguous().numpy()
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=budget // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -458,7 +484,13 @@ def main():
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--unet-dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--compute", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-launch kernel timing (roofline,\n"
+                         "shader clock, attention totals, HBM-bound launches) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (final latents and\n"
+                         "reduced 16x16 cross maps of its edit groups) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--launch-events", default="ext", choices=["ext", "fence-free", "torch"],
                     help="per-launch timing: the kernels' own dispatch timestamps through hipExtLaunchKernel\n"
                          "events (default; p2p_set_launch_events), HIP events recorded around each call without\n"
@@ -512,8 +544,11 @@ def main():
     model = pl.SyntheticStableDiffusion(device=dev, dtype=dtype)
     prompts = pl.north_star_prompts()
     B = len(prompts)
+    # the per-launch timer observes the launches of a --full run only
+    full = args.full
     timer = LaunchTimer(mode=args.launch_events)
-    _hip.LAUNCH_OBSERVER = timer
+    if full:
+        _hip.LAUNCH_OBSERVER = timer
 
     G = args.groups_per_call
 
@@ -533,12 +568,13 @@ def main():
     else:
         all_seeds = list(range(world * args.steps * G))
         warm_seeds = [10 ** 6 + rank * n_warm * G + i for i in range(n_warm * G)]
+    t_warm = time.perf_counter()
     for i in range(n_warm):
         batch(warm_seeds[i * G:(i + 1) * G])
     if distributed:
         dist.barrier()
     torch.cuda.synchronize(dev)
-    clock = ClockProbe(dev)
+    clock = ClockProbe(dev) if full else None
     timer.clock = clock
 
     def max_over_ranks(x):
@@ -548,9 +584,11 @@ def main():
             return tt.item()
         return x
 
-    timer.enabled = not graphed   # graph replays make no per-launch calls: the eager pass below times them
+    # graph replays make no per-launch calls: the eager pass below times them
+    timer.enabled = full and not graphed
     t0 = time.perf_counter()
-    clock.sample("start")
+    if full:
+        clock.sample("start")
     timer.end_batch()     # (batch 0's start mark)
 
     def progress(i, n):   # a progress line per batch (stderr; host-side only) + the batch's end event
@@ -563,7 +601,8 @@ def main():
     # all-gather of the final latents and the reduced maps (the only inter-GPU traffic)
     lat_all, maps_all = sweep.run_batched_sweep(all_seeds, batch, batch.out_shapes, rank, world, G,
                                                 device=dev, on_batch=progress)
-    clock.sample("end")
+    if full:
+        clock.sample("end")
     torch.cuda.synchronize(dev)
     if distributed:
         dist.barrier()
@@ -574,7 +613,7 @@ def main():
     eager_line = None
     mine = sweep.batches(all_seeds, rank, world, G)
     inst = mine[:args.instrumented] if graphed else mine
-    if graphed:
+    if graphed and full:
         # the per-launch timing pass: the same batches (this rank's first --instrumented), eager,
         # every hot-path launch bracketed by the kernels' own HIP events, the clock probed under
         # G1/G7; its wall time is reported beside value as eager_value
@@ -604,38 +643,59 @@ def main():
     # each source prompt's gathered map row is an average of probability rows: it sums to 1
     assert (maps_all[:, 0].sum(-1) - 1).abs().max().item() < 1e-2
 
-    avg_ms, flops, n_launch = timer.summary()
-    peak = MFMA_PEAK_BF16_TFLOPS if args.compute == "bf16" else MFMA_PEAK_F32_TFLOPS
-    # per-batch GPU time and the dominant kernel's average launch in that batch (stderr): clock
-    # droop over a long run shows up here, not in the one-line average
-    for i, ms_b, dom in timer.per_batch():
-        print(f"[bench rank {rank}] batch {i} gpu {ms_b:.1f} ms  dominant avg "
-              f"{dom * 1e3 if dom else float('nan'):.1f} us", file=sys.stderr, flush=True)
-    unet_calls = len(inst) * args.ddim_steps   # this rank's U-Net calls in the per-launch timing pass
-    attn_total = timer.attn_total(peak, unet_calls)
+    t_dump = time.perf_counter()
+    if args.dump_outputs and rank == 0:
+        # the last timed step of rank 0: its groups' rows of what the sweep returned (seed order)
+        dump_outputs(args.dump_outputs, mine[-1], {"final_latents": lat_all, "cross_maps_16": maps_all})
+    t_end = time.perf_counter()
+
+    extra = {}
+    if full:
+        avg_ms, flops, n_launch = timer.summary()
+        peak = MFMA_PEAK_BF16_TFLOPS if args.compute == "bf16" else MFMA_PEAK_F32_TFLOPS
+        # per-batch GPU time and the dominant kernel's average launch in that batch (stderr): clock
+        # droop over a long run shows up here, not in the one-line average
+        for i, ms_b, dom in timer.per_batch():
+            print(f"[bench rank {rank}] batch {i} gpu {ms_b:.1f} ms  dominant avg "
+                  f"{dom * 1e3 if dom else float('nan'):.1f} us", file=sys.stderr, flush=True)
+        unet_calls = len(inst) * args.ddim_steps   # this rank's U-Net calls in the per-launch timing pass
+        attn_total = timer.attn_total(peak, unet_calls)
+        if rank == 0:
+            achieved = flops / (avg_ms * 1e-3) / 1e12 if avg_ms else None
+            traffic, traffic_src = pmc_traffic() if G == 1 else (None, "no PMC pass at N = 8G")
+            roofline = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                        "frac": (achieved / peak) if achieved else None, "traffic": traffic,
+                        "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src,
+                        "algorithmic_bytes": 4.0 * 8 * G * 4096 * 320 * 2,
+                        "kernel": f"self40_kernel G1/G7, F16 form (P=K=4096, d=40, N={8 * G}, H=8; 8 waves x 2 x 32 queries, "
+                                  f"256-key tiles, software-pipelined 32x32 blocks)",
+                        "avg_launch_ms": avg_ms, "launches": n_launch,
+                        "probed_launches": {"avg_launch_ms": timer.summary("dominant_probed")[0],
+                                            "launches": timer.summary("dominant_probed")[2]},
+                        "flop_per_launch": flops,
+                        **_clock_fields(clock.summary(), (achieved / peak) if achieved else None),
+                        "timing": {"ext": "HIP events bound to each launch's kernels (hipExtLaunchKernel start / stop "
+                                          "events: the kernels' own dispatch timestamps, as rocprofv3's kernel trace), "
+                                          "on the launch stream",
+                                   "fence-free": "HIP events recorded around each launch on its stream, created with "
+                                                 "hipEventDisableSystemFence",
+                                   "torch": "torch.cuda.Event around each launch"}[args.launch_events]}
+            cpu = None
+            if not args.no_cpu_baseline and world == 1:
+                cpu = cpu_baseline(args.ddim_steps)
+            extra = {
+                # graphed runs: the eager loop's throughput over the per-launch timing pass that follows
+                # (the same batches' first --instrumented of this rank; every roofline field comes from it)
+                "eager_value": eager_line,
+                "roofline": roofline, "cpu_baseline": cpu,
+                # every attention launch of the timed run together (north star: ">= 45 % of bf16 MFMA peak
+                # in the attention kernels"), HIP-event timed, with the per-geometry split
+                "roofline_attn_total": attn_total,
+                # the HBM-bound launches of the path (north star: "achieved HBM GB/s for the map and blend
+                # kernels"), HIP-event timed in the same run; algorithmic bytes, not PMC
+                "roofline_hbm": timer.hbm_lines(),
+            }
     if rank == 0:
-        achieved = flops / (avg_ms * 1e-3) / 1e12 if avg_ms else None
-        traffic, traffic_src = pmc_traffic() if G == 1 else (None, "no PMC pass at N = 8G")
-        roofline = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                    "frac": (achieved / peak) if achieved else None, "traffic": traffic,
-                    "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src,
-                    "algorithmic_bytes": 4.0 * 8 * G * 4096 * 320 * 2,
-                    "kernel": f"self40_kernel G1/G7, F16 form (P=K=4096, d=40, N={8 * G}, H=8; 8 waves x 2 x 32 queries, "
-                              f"256-key tiles, software-pipelined 32x32 blocks)",
-                    "avg_launch_ms": avg_ms, "launches": n_launch,
-                    "probed_launches": {"avg_launch_ms": timer.summary("dominant_probed")[0],
-                                        "launches": timer.summary("dominant_probed")[2]},
-                    "flop_per_launch": flops,
-                    **_clock_fields(clock.summary(), (achieved / peak) if achieved else None),
-                    "timing": {"ext": "HIP events bound to each launch's kernels (hipExtLaunchKernel start / stop "
-                                      "events: the kernels' own dispatch timestamps, as rocprofv3's kernel trace), "
-                                      "on the launch stream",
-                               "fence-free": "HIP events recorded around each launch on its stream, created with "
-                                             "hipEventDisableSystemFence",
-                               "torch": "torch.cuda.Event around each launch"}[args.launch_events]}
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            cpu = cpu_baseline(args.ddim_steps)
         n_steps = max(1, len(sweep.batches(all_seeds, 0, world, G)))
         workload = ("configs[3]: seed sweep of " + str(n_total) + " edit groups, " if args.seeds > 0 else
                     "configs[1]: ")
@@ -653,16 +713,11 @@ def main():
             "loop": ("HIP graphs: the 50 DDIM steps of each batch replay graphs captured once per batch size "
                      "(pipeline.GraphedEditRunner; bit-identical to the eager loop, tests/test_gpu_pipeline.py)"
                      if graphed else "eager"),
-            # graphed runs: the eager loop's throughput over the per-launch timing pass that follows
-            # (the same batches' first --instrumented of this rank; every roofline field comes from it)
-            "eager_value": eager_line,
-            "roofline": roofline, "cpu_baseline": cpu,
-            # every attention launch of the timed run together (north star: ">= 45 % of bf16 MFMA peak
-            # in the attention kernels"), HIP-event timed, with the per-geometry split
-            "roofline_attn_total": attn_total,
-            # the HBM-bound launches of the path (north star: "achieved HBM GB/s for the map and blend
-            # kernels"), HIP-event timed in the same run; algorithmic bytes, not PMC
-            "roofline_hbm": timer.hbm_lines(),
+            # host seconds of this process outside the timed steps (--full's extra passes not counted)
+            "seconds": {"setup": t_warm - T_START, "warmup": t0 - t_warm, "timed": elapsed,
+                        "dump_outputs": t_end - t_dump},
+            "full": full,
+            **extra,
         }
         print(json.dumps(line))
     if distributed:

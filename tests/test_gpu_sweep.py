@@ -82,7 +82,7 @@ def test_bench_under_torchrun_world1_rccl(cuda):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(root, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--ddim-steps", "2", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--ddim-steps", "2", "--full", "--no-cpu-baseline"]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)

@@ -9,8 +9,8 @@
 #     tests[:<pytest -k>]    pytest -m gpu (optionally -k filtered)
 #     files:<f1,f2,..>       pytest -m gpu on the listed test files
 #     ab:<v1,v2,..>          G1 A/B (tools/g1_ab.py), one process per P2P_SELF_VARIANT (experiments lib)
-#     bench[:<args>]         python bench.py <args> (default: the driver's default run), JSON -> bench.json
-#     prof[:<args>]          rocprofv3 --kernel-trace --stats of bench.py <args>
+#     bench[:<args>]         python bench.py --full <args> (roofline and CPU baseline included), JSON -> bench.json
+#     prof[:<args>]          rocprofv3 --kernel-trace --stats of bench.py --full <args>
 #     pmc:<name>:<counters>  one rocprofv3 --pmc pass (comma-separated counters) over tools/g1_only.py
 #                            (G1 launches only; P2P_SELF_VARIANT / P2P_EXPERIMENTS_LIB from the env)
 #     cross                  tools/cross_bench.py (cross-attention launch shapes)
@@ -49,9 +49,9 @@ for step in "$@"; do
         run 150 "$out/ab_$v.log" env P2P_EXPERIMENTS_LIB=1 P2P_SELF_VARIANT=$v python -u tools/g1_ab.py
         tail -1 "$out/ab_$v.log" | tee -a "$out/ab.log"
       done ;;
-    bench) run 900 "$out/bench.log" python -u bench.py $arg; grep '^{' "$out/bench.log" | tail -1 | tee "$out/bench.json" ;;
+    bench) run 900 "$out/bench.log" python -u bench.py --full $arg; grep '^{' "$out/bench.log" | tail -1 | tee "$out/bench.json" ;;
     prof)
-      run 900 "$out/prof.log" rocprofv3 --kernel-trace --stats -d "$out/prof" -o run -- python3 -u bench.py $arg
+      run 900 "$out/prof.log" rocprofv3 --kernel-trace --stats -d "$out/prof" -o run -- python3 -u bench.py --full $arg
       grep '^{' "$out/prof.log" | tail -1 | tee "$out/bench_under_rocprof.json"
       find "$out/prof" -name "*kernel_stats.csv" -exec cp {} "$out/kernel_stats.csv" \;
       db=$(find "$out/prof" -name "*.db" | head -1)
@@ -94,7 +94,7 @@ for step in "$@"; do
     variants)
       vs=${arg%%:*}; prefix=""; [ "$vs" != "$arg" ] && prefix=${arg#*:}
       for v in ${vs//,/ }; do
-        run 600 "$out/variant_$v.log" env P2P_EXPERIMENTS_LIB=1 P2P_SELF_VARIANT=$v python -u bench.py --gpus 1 --steps 4 --warmup 2 --no-cpu-baseline
+        run 600 "$out/variant_$v.log" env P2P_EXPERIMENTS_LIB=1 P2P_SELF_VARIANT=$v python -u bench.py --gpus 1 --steps 4 --warmup 2 --full --no-cpu-baseline
         grep '^{' "$out/variant_$v.log" | tail -1 | python3 -c "
 import json, sys; d = json.loads(sys.stdin.read())
 print('variant $v', round(d['value'], 4), [(g['geometry'], round(g['avg_launch_ms'] * 1e3, 1))

@@ -10,7 +10,7 @@
 set -u
 export TMPDIR=/tmp
 tag=${1:-flagab}
-args=${BENCH_ARGS:---gpus 1 --steps 3 --warmup 1 --no-cpu-baseline}
+args=${BENCH_ARGS:---gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline}
 out=gpurun_out/$tag
 mkdir -p "$out"
 i=0
