@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define P2P_ABI_VERSION 15
+#define P2P_ABI_VERSION 16
 #define P2P_MAX_BATCH 64  /* entries per launch (U-Net batch: 2 x prompts x groups)   */
 #define P2P_MAX_GROUPS 32 /* prompt groups per cross-attention launch                 */
 #define P2P_MAX_KEYS_CROSS 96
@@ -47,7 +47,13 @@ enum {
   P2P_GROUP_F_SHARED_KV = 4
 };
 
-enum { P2P_DTYPE_F32 = 0, P2P_DTYPE_BF16 = 1 };
+/* Element types of q, k, v, o (and of the latent step's eps).  P2P_DTYPE_F16 (ABI 16): IEEE
+ * binary16, what a Stable Diffusion model loaded with torch_dtype=torch.float16 produces. */
+enum { P2P_DTYPE_F32 = 0, P2P_DTYPE_BF16 = 1, P2P_DTYPE_F16 = 2 };
+/* P2P_COMPUTE_BF16 names the 16-bit MFMA pipe; the operand format follows the inputs: bf16
+ * MFMAs for bf16 (and, split, for f32) inputs, f16 MFMAs for f16 inputs (the name predates
+ * ABI 16 and is kept).  P2P_COMPUTE_F32 is the exact-f32 check mode, f32 inputs only: bf16 or
+ * f16 inputs with it are rejected (P2P_E_DTYPE). */
 enum { P2P_COMPUTE_BF16 = 0, P2P_COMPUTE_F32 = 1 };
 
 enum {
@@ -73,7 +79,7 @@ typedef struct {
   int64_t q_batch_stride, k_batch_stride, v_batch_stride, o_batch_stride;
   int32_t n_batch, n_query, n_key, n_heads, head_dim;
   int32_t io_dtype; /* P2P_DTYPE_*  (element type of q, k, v, o)                      */
-  int32_t compute;  /* P2P_COMPUTE_* (bf16 MFMA, or exact-f32 MFMA check mode)          */
+  int32_t compute;  /* P2P_COMPUTE_* (16-bit MFMA pipe, or exact-f32 MFMA check mode)   */
   float scale;
 } p2p_attn_tensors;
 
@@ -160,7 +166,8 @@ int p2p_attn_pv(const p2p_attn_tensors* t, const float* probs, p2p_stream_t stre
  * the null embedding through every patched attention of the U-Net).  Forward: O as
  * p2p_self_attn_fwd with no controller edit, plus lse [n_batch * n_heads, n_query] f32, the row
  * log-sum-exp in the log2 domain with the scale folded in (softmax row = exp2(scale * log2(e) *
- * s - lse)).  Any n_key (self- or cross-attention); bf16 compute only. */
+ * s - lse)).  Any n_key (self- or cross-attention); bf16 compute only, f32 or bf16 tensors
+ * (P2P_DTYPE_F16 is rejected with P2P_E_DTYPE here and by the backward: ABI 16). */
 int p2p_attn_fwd_lse(const p2p_attn_tensors* t, float* lse, p2p_stream_t stream);
 
 /* Backward of O = softmax(Q K^T * scale) V for the same tensors (t->o = the forward's O):
@@ -215,7 +222,7 @@ int p2p_localblend(const p2p_blend_args* a, p2p_stream_t stream);
  * x / out [B, C, H, W] f32 (out may alias x), mask uint8 [B, H, W] (p2p_localblend mask_out).
  * The four coefficients are the host-side 0-dim values the scheduler computes (beta_t ** 0.5 ...).
  * Intermediates are rounded as the reference's eager torch ops round them (bf16 products for a
- * bf16 eps), so the result is bit-identical to the unfused sequence. */
+ * bf16 eps, f16 products for an f16 eps), so the result is bit-identical to the unfused sequence. */
 typedef struct {
   const void* eps;
   int32_t eps_dtype;               /* P2P_DTYPE_*                                      */

@@ -25,6 +25,8 @@ template <>
 __device__ __forceinline__ float one_elem<float>() { return 1.0f; }
 template <>
 __device__ __forceinline__ uint16_t one_elem<uint16_t>() { return 0x3F80; }  // bf16 1.0
+template <>
+__device__ __forceinline__ f16_t one_elem<f16_t>() { return f16_t(0x3C00); }  // f16 1.0
 
 // ====================================================================== self attention
 enum { MODE_FUSED = 0, MODE_PV = 3 };
@@ -444,7 +446,9 @@ __global__ __launch_bounds__(64 * WAVES) void self_attn_multi_kernel(SelfArgs a)
   constexpr int DK = (D + 15) / 16 * 16;
   constexpr int DV = (D + 31) / 32 * 32;
   static_assert(DV > D, "needs the ones column");
-  static_assert(!F16 || (DK > D && MQ::planes == 1 && sizeof(IO) == 2), "F16: bf16 inputs, a padding column");
+  static_assert(!std::is_same<IO, f16_t>::value, "bf16 / f32 inputs only (bf16 V image and P; fp16: p2p_self40.hip)");
+  static_assert(!F16 || (DK > D && MQ::planes == 1 && std::is_same<IO, uint16_t>::value),
+                "F16: bf16 inputs, a padding column");
   constexpr int NKT = DK / 16;
   constexpr int NDT = DV / 32;
   constexpr int NSB = BK / 32;
@@ -1143,15 +1147,15 @@ __global__ __launch_bounds__(64 * WAVES, (DENSE && D <= 80) ? 2 : 1) void cross_
   // Same-box rocprof (profiles/r05/ostore_ab/): d = 80 edit steps 16.43 -> 14.90 us, d = 160 17.44 ->
   // 16.56; the 8x8 layers (P = 64: half of every 128-query workgroup's rows past P) ran 2 % slower
   // and keep the direct store
-  const bool o16 = std::is_same<IO, uint16_t>::value && a.P >= 256 && (a.ldo & 7) == 0 &&
+  const bool o16 = is_io16<IO>::value && a.P >= 256 && (a.ldo & 7) == 0 &&
                    (a.bso & 7) == 0 && ((uintptr_t)a.o & 15) == 0;
   auto store_o = [&](const f32x16_t (&O)[NDT], float inv) __attribute__((always_inline)) {
-    if constexpr (std::is_same<IO, uint16_t>::value) {
+    if constexpr (is_io16<IO>::value) {
       if (o16) {
         constexpr int OS = D + 8;   // 16-byte aligned rows on distinct banks
         static_assert(WAVES * 32 * OS * 2 <= KBYTES + VBYTES, "the output rows fit the K / V image");
         __syncthreads();
-        uint16_t* const orow = reinterpret_cast<uint16_t*>(smem) + wave * 32 * OS;
+        IO* const orow = reinterpret_cast<IO*>(smem) + wave * 32 * OS;
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
@@ -1164,7 +1168,7 @@ __global__ __launch_bounds__(64 * WAVES, (DENSE && D <= 80) ? 2 : 1) void cross_
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        uint16_t* const ob = static_cast<uint16_t*>(a.o) + (int64_t)n * a.bso + h * D;
+        IO* const ob = static_cast<IO*>(a.o) + (int64_t)n * a.bso + h * D;
 #pragma unroll
         for (int c0 = 0; c0 < 32 * CPR; c0 += 64) {
           const int cidx = c0 + lane;
@@ -1233,7 +1237,7 @@ __global__ __launch_bounds__(64 * WAVES, (DENSE && D <= 80) ? 2 : 1) void cross_
       }
       for (int i = tid; i < (KR - K) * VS / 8; i += NT)   // V rows K..KR (weighted by p = 0)
         *reinterpret_cast<short8_t*>(Vs + K * VS + 8 * i) = short8_t{};
-      for (int r = tid; r < K; r += NT) Vs[r * VS + D] = 0x3F80;   // bf16 1.0: the row-sum column
+      for (int r = tid; r < K; r += NT) Vs[r * VS + D] = one_elem<EV>();   // 1.0: the row-sum column
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
         const int cidx = tid + i * NT;
@@ -1335,7 +1339,7 @@ __global__ __launch_bounds__(64 * WAVES, (DENSE && D <= 80) ? 2 : 1) void cross_
   // its LocalBlend word-sum entries) into registers, so the store epilogue only adds and writes.
   // (bf16 inputs only: the f32-input instantiations have no registers to spare for the rows)
   // 1: touches after the first barrier, 3: the values themselves
-  constexpr int touch_when = std::is_same<IO, uint16_t>::value ? 3 : 1;
+  constexpr int touch_when = is_io16<IO>::value ? 3 : 1;
   constexpr int kRmwF4 = 32 * KR / 4;
   f32x4_t rmwbuf[(kRmwF4 + 63) / 64];
   float bsum_old = 0.f;
@@ -1396,7 +1400,8 @@ __global__ __launch_bounds__(64 * WAVES, (DENSE && D <= 80) ? 2 : 1) void cross_
   // (rows >= P / >= K read as zeros).  Loads inside a branch per fragment or chunk made hipcc
   // re-load kernel arguments and drain the earlier loads with vmcnt(0) between them: the stored
   // source / plain entries' staging ran as a chain of round trips
-  constexpr bool kBufIO = std::is_same<IO, uint16_t>::value && std::is_same<MQ, QkBf16<uint16_t>>::value;
+  constexpr bool kBufIO = (std::is_same<IO, uint16_t>::value && std::is_same<MQ, QkBf16<uint16_t>>::value) ||
+                          (std::is_same<IO, f16_t>::value && std::is_same<MQ, QkF16>::value);
   auto load_q = [&](int e, typename MQ::frag (&qf)[NKT]) {
     const IO* qp = static_cast<const IO*>(a.q) + (int64_t)e * a.bsq + h * D;
     if constexpr (kBufIO) {
@@ -1878,8 +1883,9 @@ static void launch_fused(const SelfArgs& a, hipStream_t st) {
   constexpr bool kOnes = ((D + 31) / 32 * 32) > D;
   if (a.n_maps > 0)  // the lse feeds stored maps: exact f32 row sums
     launch_kernel((self_attn_fused_kernel<IO, MQ, MP, D, BK, W, true>), grid, block, 0, st, b);
-  else if constexpr (kOnes && MP::kElemBytes == 2) {
-    // O only (no lse): no per-tile max
+  else if constexpr (kOnes && std::is_same<MP, MmaBf16>::value) {
+    // O only (no lse): no per-tile max (bf16 P: p grows with the f32 exponent range; f16 P keeps
+    // the defer-max loop, p <= 2^8)
     if (a.lse == nullptr)
       launch_kernel((self_attn_fused_kernel<IO, MQ, MP, D, BK, W, false, true>), grid, block, 0, st, b);
     else
@@ -1903,11 +1909,15 @@ static hipError_t launch_self_d(const SelfArgs& a, int mode, hipStream_t st) {
   if constexpr (MP::kElemBytes == 2 && D == 40) {
     // d = 40 on the bf16 pipe, nothing but O wanted (G1/G7 without kept maps or autograd)
     if (mode == MODE_FUSED && a.lse == nullptr && a.n_maps == 0 && a.P > 64) {
-      constexpr bool kF16 = MQ::planes == 1 && sizeof(IO) == 2;
+      constexpr bool kF16 = MQ::planes == 1 && std::is_same<IO, uint16_t>::value;
       // bf16 inputs: the software-pipelined F16-form kernel (p2p_self40.hip)
       if constexpr (kF16)
         if (self40_eligible(a, 40)) return (hipError_t)run_self40(a, 40, st);
-      if (a.P >= 2048) {
+      // fp16 inputs: the same kernel's fp16 instantiation, or the per-tile kernel below (the
+      // multi-block kernel is bf16 / f32 only)
+      if constexpr (std::is_same<IO, f16_t>::value)
+        if (self40_eligible(a, 40)) return (hipError_t)run_self40(a, 40, st, true);
+      if constexpr (!std::is_same<IO, f16_t>::value) if (a.P >= 2048) {
         // f32 inputs (split-bf16 Q K^T, two K planes): the multi-block kernel, 128-key tiles;
         // bf16 inputs with K < 256: the same with the F16 form
         if constexpr (MQ::planes == 1) launch_multi<IO, MQ, D, 256, 8, 2, kF16, true>(a, st);
@@ -1916,13 +1926,18 @@ static hipError_t launch_self_d(const SelfArgs& a, int mode, hipStream_t st) {
       }
     }
   }
-  if constexpr (MP::kElemBytes == 2 && D == 80 && MQ::planes == 1 && sizeof(IO) == 2) {
+  if constexpr (D == 80 && std::is_same<MQ, QkBf16<uint16_t>>::value) {
     // d = 80, bf16 inputs, nothing but O wanted (G2/G6 without kept maps or autograd): the
     // software-pipelined kernel of p2p_self40.hip in its bf16 form
     if (mode == MODE_FUSED && a.lse == nullptr && a.n_maps == 0 && self40_eligible(a, 80))
       return (hipError_t)run_self40(a, 80, st);
   }
-  if constexpr (MP::kElemBytes == 2 && D == 160 && MQ::planes == 1 && sizeof(IO) == 2) {
+  if constexpr (D == 80 && std::is_same<MQ, QkF16>::value) {
+    // the same for fp16 inputs (raw f16 Q and K on the f16 MFMA)
+    if (mode == MODE_FUSED && a.lse == nullptr && a.n_maps == 0 && self40_eligible(a, 80))
+      return (hipError_t)run_self40(a, 80, st, true);
+  }
+  if constexpr (D == 160 && std::is_same<MQ, QkBf16<uint16_t>>::value) {
     // d = 160, bf16 inputs, O only (the 16x16 / 8x8 layers without kept maps or autograd): the
     // waves of a 32-query workgroup split the keys (p2p_selfsplit.hip, K <= 128), or the per-tile
     // kernel with its 4-stage DMA ring (K = 256)
@@ -2048,13 +2063,16 @@ static int dispatch_cross(const CrossArgs& a, int d, hipStream_t st) {
 }
 
 // Precision selection: exact-f32 check mode; bf16 pipe on f32 inputs (split-bf16 QK^T so the
-// logits keep f32 grade, bf16 PV); bf16 inputs (one bf16 MFMA per step, exact products).
+// logits keep f32 grade, bf16 PV); bf16 inputs (one bf16 MFMA per step, exact products); fp16
+// inputs (one f16 MFMA per step, exact products, f16 PV).
 int run_self(const SelfArgs& a, int io_dtype, int compute, int d, int mode, hipStream_t st) {
   if (compute == P2P_COMPUTE_F32) {
     if (io_dtype != P2P_DTYPE_F32) return P2P_E_DTYPE;
     return dispatch_self<float, QkF32, MmaF32>(a, d, mode, st);
   }
   if (io_dtype == P2P_DTYPE_F32) return dispatch_self<float, QkSplit, MmaBf16>(a, d, mode, st);
+  if (io_dtype == P2P_DTYPE_F16) return dispatch_self<f16_t, QkF16, MmaF16>(a, d, mode, st);
+  if (io_dtype != P2P_DTYPE_BF16) return P2P_E_DTYPE;
   return dispatch_self<uint16_t, QkBf16<uint16_t>, MmaBf16>(a, d, mode, st);
 }
 
@@ -2064,6 +2082,8 @@ int run_self_probs(const SelfArgs& a, int io_dtype, int compute, int d, hipStrea
     return dispatch_self_probs<float, QkF32>(a, d, st);
   }
   if (io_dtype == P2P_DTYPE_F32) return dispatch_self_probs<float, QkSplit>(a, d, st);
+  if (io_dtype == P2P_DTYPE_F16) return dispatch_self_probs<f16_t, QkF16>(a, d, st);
+  if (io_dtype != P2P_DTYPE_BF16) return P2P_E_DTYPE;
   return dispatch_self_probs<uint16_t, QkBf16<uint16_t>>(a, d, st);
 }
 
@@ -2074,6 +2094,8 @@ int run_self_maps(const SelfArgs& a, int io_dtype, int compute, int d, hipStream
     return dispatch_self_maps<float, QkF32>(a, d, st);
   }
   if (io_dtype == P2P_DTYPE_F32) return dispatch_self_maps<float, QkSplit>(a, d, st);
+  if (io_dtype == P2P_DTYPE_F16) return dispatch_self_maps<f16_t, QkF16>(a, d, st);
+  if (io_dtype != P2P_DTYPE_BF16) return P2P_E_DTYPE;
   return dispatch_self_maps<uint16_t, QkBf16<uint16_t>>(a, d, st);
 }
 
@@ -2083,6 +2105,9 @@ int run_cross(const CrossArgs& a, int io_dtype, int compute, int d, hipStream_t 
     return dispatch_cross<float, QkF32, MmaF32>(a, d, st);
   }
   if (io_dtype == P2P_DTYPE_F32) return dispatch_cross<float, QkSplit, MmaBf16>(a, d, st);
+  // (the group-coupled kernel is bf16-only: fp16 takes the per-entry kernel)
+  if (io_dtype == P2P_DTYPE_F16) return dispatch_cross<f16_t, QkF16, MmaF16>(a, d, st);
+  if (io_dtype != P2P_DTYPE_BF16) return P2P_E_DTYPE;
   if (cross_group_eligible(a, d)) return run_cross_group(a, d, st);
   return dispatch_cross<uint16_t, QkBf16<uint16_t>, MmaBf16>(a, d, st);
 }

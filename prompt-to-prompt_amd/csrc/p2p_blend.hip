@@ -293,10 +293,11 @@ __global__ void clock_probe_kernel(unsigned long long* __restrict__ out, unsigne
 // NullInversion.prev_step, null_text.py:471-479; the same formula with the inversion's
 // coefficients is next_step, :481-489) and the LocalBlend latent blend with a precomputed mask
 // (null_text.py:68-70 / main.py:50-52).  Every intermediate is rounded where the reference's
-// torch ops round it: to bf16 for the products torch keeps in the U-Net's bf16 output dtype,
+// torch ops round it: to bf16 (f16) for the products torch keeps in the U-Net's bf16 (f16) output dtype,
 // to f32 elsewhere, with no fma contraction -- so the update is bit-identical to the eager
 // sequence on the same inputs.
 __device__ __forceinline__ float rnd_bf16(float x) { return bf2f(f2bf(x)); }
+__device__ __forceinline__ float rnd_f16(float x) { return h2f(f2h(x)); }
 
 // explicit round-to-nearest ops: no fma contraction whatever the compile flags
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
@@ -316,9 +317,10 @@ struct DdimC {
         sqrt_alpha_prev(a.sqrt_alpha_prev), sqrt_one_minus_alpha_prev(a.sqrt_one_minus_alpha_prev) {}
 };
 
-template <bool BF16, typename A>
+// DT: the eps element type (P2P_DTYPE_*), i.e. the format torch's eager ops round to
+template <int DT, typename A>
 __device__ __forceinline__ float ddim_from(const A& a, float eu, float ec, float x) {
-  auto rd = [](float v) { return BF16 ? rnd_bf16(v) : v; };
+  auto rd = [](float v) { return DT == P2P_DTYPE_BF16 ? rnd_bf16(v) : DT == P2P_DTYPE_F16 ? rnd_f16(v) : v; };
   float noise;
   if (a.cfg) {
     const float diff = rd(sub_rn(ec, eu));
@@ -327,28 +329,29 @@ __device__ __forceinline__ float ddim_from(const A& a, float eu, float ec, float
   } else {
     noise = eu;
   }
-  // a 0-dim f32 factor times a bf16 tensor: torch casts the factor to bf16 first
+  // a 0-dim f32 factor times a bf16 (f16) tensor: torch casts the factor to bf16 (f16) first
   const float t1 = rd(mul_rn(rd(a.sqrt_beta_t), noise));
   const float x0 = __fdiv_rn(sub_rn(x, t1), a.sqrt_alpha_t);
   const float dir = rd(mul_rn(rd(a.sqrt_one_minus_alpha_prev), noise));
   return add_rn(mul_rn(a.sqrt_alpha_prev, x0), dir);
 }
 
-template <bool BF16>
+template <int DT>
 __device__ __forceinline__ float eps_at(const p2p_latent_step_args& a, int64_t idx) {
-  if constexpr (BF16) return bf2f(static_cast<const uint16_t*>(a.eps)[idx]);
+  if constexpr (DT == P2P_DTYPE_BF16) return bf2f(static_cast<const uint16_t*>(a.eps)[idx]);
+  else if constexpr (DT == P2P_DTYPE_F16) return h2f(static_cast<const uint16_t*>(a.eps)[idx]);
   else return static_cast<const float*>(a.eps)[idx];
 }
 
 // prev_sample of prompt b at element i of its [C, H, W] latent
-template <bool BF16>
+template <int DT>
 __device__ __forceinline__ float ddim_prev(const p2p_latent_step_args& a, int b, int64_t i, int64_t chw) {
-  const float eu = eps_at<BF16>(a, (int64_t)b * chw + i);
-  const float ec = a.cfg ? eps_at<BF16>(a, (int64_t)(a.n_prompts + b) * chw + i) : 0.f;
-  return ddim_from<BF16>(a, eu, ec, a.x[(int64_t)b * chw + i]);
+  const float eu = eps_at<DT>(a, (int64_t)b * chw + i);
+  const float ec = a.cfg ? eps_at<DT>(a, (int64_t)(a.n_prompts + b) * chw + i) : 0.f;
+  return ddim_from<DT>(a, eu, ec, a.x[(int64_t)b * chw + i]);
 }
 
-template <bool BF16>
+template <int DT>
 __global__ __launch_bounds__(256) void latent_step_kernel(p2p_latent_step_args a, int64_t chw) {
   const int HW = a.height * a.width;
   const int B = a.n_prompts;
@@ -360,7 +363,7 @@ __global__ __launch_bounds__(256) void latent_step_kernel(p2p_latent_step_args a
     bool blend = false;
     for (int b = 0; b < B; ++b) {
       const int bg = b % gs;                              // position inside its group
-      float prev = ddim_prev<BF16>(a, b, i, chw);
+      float prev = ddim_prev<DT>(a, b, i, chw);
       if (bg == 0) {
         prev0 = prev;                                     // the group's source prompt
         blend = a.mask && (!a.group_blend || a.group_blend[b / gs]);
@@ -382,7 +385,7 @@ __global__ __launch_bounds__(256) void latent_step_kernel(p2p_latent_step_args a
 // issues its eps / x loads (4 pixels x 1 channel, for b and the source) before the mask build's,
 // so the launch waits about two memory round trips; 64 workgroups keep the per-thread DDIM
 // arithmetic (two IEEE divisions per element) short.
-template <bool BF16>
+template <int DT>
 __global__ __launch_bounds__(256, 1) void latent_blend_kernel(p2p_latent_step_args a, int64_t chw, int px_per_wg) {
   // every field this kernel reads, copied to scalars first (see DdimC)
   const int HW = a.height * a.width;
@@ -405,15 +408,19 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(p2p_latent_step_ar
   const int pxc = min(px, HW - 4);
   // raw loads first, unconditionally (clamped to valid addresses; the unused ones are discarded),
   // so no load sits in a branch with its own wait: every load of the pass is in flight at once
-  using Raw = typename std::conditional<BF16, uint2, f32x4_t>::type;
+  constexpr bool k16 = DT != P2P_DTYPE_F32;
+  using Raw = typename std::conditional<k16, uint2, f32x4_t>::type;
   auto ld_eps = [eg](int64_t idx) __attribute__((always_inline)) -> Raw {
-    if constexpr (BF16) return *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(eg) + idx);
+    if constexpr (k16) return *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(eg) + idx);
     else return *reinterpret_cast<const f32x4_t*>(static_cast<const float*>(eg) + idx);
   };
   auto unpack = [](const Raw& r) __attribute__((always_inline)) -> f32x4_t {
-    if constexpr (BF16)
+    if constexpr (DT == P2P_DTYPE_BF16)
       return f32x4_t{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
                      __uint_as_float(r.y & 0xffff0000u)};
+    else if constexpr (DT == P2P_DTYPE_F16)
+      return f32x4_t{h2f((uint16_t)(r.x & 0xffffu)), h2f((uint16_t)(r.x >> 16)), h2f((uint16_t)(r.y & 0xffffu)),
+                     h2f((uint16_t)(r.y >> 16))};
     else return r;
   };
   for (int c0 = 0; c0 < C; c0 += 4) {
@@ -437,10 +444,10 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(p2p_latent_step_ar
     f32x4_t o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float prev = ddim_from<BF16>(dc, eu[j], ec[j], xv[0][j]);
+      float prev = ddim_from<DT>(dc, eu[j], ec[j], xv[0][j]);
       if (blend) {
         const f32x4_t eu0 = unpack(reu[1]), ec0 = unpack(rec[1]);
-        const float prev0 = ddim_from<BF16>(dc, eu0[j], ec0[j], xv[1][j]);
+        const float prev0 = ddim_from<DT>(dc, eu0[j], ec0[j], xv[1][j]);
         const float m = L.msrc[blend_src_of(px + j, res, H, W)];
         prev = add_rn(prev0, mul_rn(m, sub_rn(prev, prev0)));
       }
@@ -454,7 +461,8 @@ int run_latent_step(const p2p_latent_step_args& a, hipStream_t st) {
   if (!a.eps || !a.x || !a.out || a.n_prompts < 1 || a.channels < 1 || a.height < 1 || a.width < 1 ||
       a.group_size < 0 || (a.group_size > 0 && a.n_prompts % a.group_size))
     return P2P_E_ARG;
-  if (a.eps_dtype != P2P_DTYPE_F32 && a.eps_dtype != P2P_DTYPE_BF16) return P2P_E_DTYPE;
+  if (a.eps_dtype != P2P_DTYPE_F32 && a.eps_dtype != P2P_DTYPE_BF16 && a.eps_dtype != P2P_DTYPE_F16)
+    return P2P_E_DTYPE;
   const int64_t chw = (int64_t)a.channels * a.height * a.width;
   const int gs = a.group_size > 0 ? a.group_size : a.n_prompts;
   const int n_groups = a.n_prompts / gs;
@@ -475,17 +483,21 @@ int run_latent_step(const p2p_latent_step_args& a, hipStream_t st) {
     const int hw = a.height * a.width;
     dim3 grid((hw + kPx - 1) / kPx, a.n_prompts);
     if (a.eps_dtype == P2P_DTYPE_BF16)
-      launch_kernel(latent_blend_kernel<true>, grid, dim3(256), 0, st, a, chw, kPx);
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_BF16>, grid, dim3(256), 0, st, a, chw, kPx);
+    else if (a.eps_dtype == P2P_DTYPE_F16)
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_F16>, grid, dim3(256), 0, st, a, chw, kPx);
     else
-      launch_kernel(latent_blend_kernel<false>, grid, dim3(256), 0, st, a, chw, kPx);
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_F32>, grid, dim3(256), 0, st, a, chw, kPx);
     return (int)hipGetLastError();
   }
   int64_t blocks = (chw + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (a.eps_dtype == P2P_DTYPE_BF16)
-    launch_kernel(latent_step_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+    launch_kernel(latent_step_kernel<P2P_DTYPE_BF16>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+  else if (a.eps_dtype == P2P_DTYPE_F16)
+    launch_kernel(latent_step_kernel<P2P_DTYPE_F16>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
   else
-    launch_kernel(latent_step_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+    launch_kernel(latent_step_kernel<P2P_DTYPE_F32>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
   return (int)hipGetLastError();
 }
 

@@ -423,6 +423,7 @@ static int dispatch_bwd(const BwdArgs& a, int d, hipStream_t st) {
 
 int run_attn_bwd(const BwdArgs& a, int io_dtype, int d, hipStream_t st) {
   if (io_dtype == P2P_DTYPE_F32) return dispatch_bwd<float>(a, d, st);
+  if (io_dtype != P2P_DTYPE_BF16) return P2P_E_DTYPE;   // (fp16: no backward kernels)
   return dispatch_bwd<uint16_t>(a, d, st);
 }
 

@@ -17,8 +17,11 @@ int check_tensors(const p2p_attn_tensors* t, bool need_q, bool need_k, bool need
   if (t->n_batch < 1 || t->n_query < 1 || t->n_key < 1 || t->n_heads < 1 || t->head_dim < 8) return P2P_E_ARG;
   if (t->n_batch > P2P_MAX_BATCH) return P2P_E_BATCH;
   if (t->head_dim % 8) return P2P_E_HEAD_DIM;
-  if (t->io_dtype != P2P_DTYPE_F32 && t->io_dtype != P2P_DTYPE_BF16) return P2P_E_DTYPE;
+  if (t->io_dtype != P2P_DTYPE_F32 && t->io_dtype != P2P_DTYPE_BF16 && t->io_dtype != P2P_DTYPE_F16)
+    return P2P_E_DTYPE;
   if (t->compute != P2P_COMPUTE_BF16 && t->compute != P2P_COMPUTE_F32) return P2P_E_DTYPE;
+  // the exact-f32 check mode takes f32 tensors only; 16-bit tensors run on the 16-bit MFMA pipe
+  if (t->compute == P2P_COMPUTE_F32 && t->io_dtype != P2P_DTYPE_F32) return P2P_E_DTYPE;
   const int es = t->io_dtype == P2P_DTYPE_F32 ? 4 : 2;
   // 16-byte vector loads of 8-element chunks need every row/head offset 8-element aligned
   const int64_t strides[8] = {t->q_row_stride, t->k_row_stride, t->v_row_stride, t->o_row_stride,
@@ -246,6 +249,7 @@ int p2p_localblend(const p2p_blend_args* a, p2p_stream_t stream) {
 int p2p_attn_fwd_lse(const p2p_attn_tensors* t, float* lse, p2p_stream_t stream) {
   int rc = check_tensors(t, true, true, true, true);
   if (rc) return rc;
+  if (t->io_dtype == P2P_DTYPE_F16) return P2P_E_DTYPE;   // autograd pair: f32 / bf16 tensors only
   if (!lse) return P2P_E_ARG;
   if (t->compute != P2P_COMPUTE_BF16) return P2P_E_DTYPE;
   SelfArgs a;
@@ -263,6 +267,7 @@ int p2p_attn_fwd_lse(const p2p_attn_tensors* t, float* lse, p2p_stream_t stream)
 
 int64_t p2p_attn_bwd_workspace(const p2p_attn_tensors* t) {
   if (!t || t->n_batch < 1 || t->n_query < 1 || t->n_key < 1 || t->n_heads < 1 || t->head_dim < 1) return 0;
+  if (t->io_dtype == P2P_DTYPE_F16) return P2P_E_DTYPE;   // no fp16 backward (p2p_attn_bwd rejects it too)
   const int split = bwd_kv_split(t->n_batch, t->n_heads, t->n_query, t->n_key, t->head_dim);
   if (split <= 1) return 0;
   return (int64_t)2 * split * t->n_batch * t->n_key * t->n_heads * t->head_dim * (int64_t)sizeof(float);
@@ -273,6 +278,8 @@ int p2p_attn_bwd(const p2p_attn_tensors* t, const void* dout, const float* lse, 
                  p2p_stream_t stream) {
   int rc = check_tensors(t, true, true, true, true);
   if (rc) return rc;
+  // the backward kernels read every 16-bit tensor as bf16: fp16 bits must never reach them
+  if (t->io_dtype == P2P_DTYPE_F16) return P2P_E_DTYPE;
   if (!dout || !lse || !delta || !dq || !dk || !dv) return P2P_E_ARG;
   const int64_t need = p2p_attn_bwd_workspace(t);
   if (need > 0 && (!workspace || workspace_bytes < need)) return P2P_E_ARG;

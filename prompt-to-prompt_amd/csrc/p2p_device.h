@@ -35,6 +35,19 @@ __device__ __forceinline__ float bf2f(uint16_t x) {
   return __builtin_bit_cast(float, ((uint32_t)x) << 16);
 }
 
+// IEEE binary16 I/O element.  uint16_t means bf16 throughout the kernels; fp16 tensors carry this
+// distinct 2-byte tag instead, so every trait below is chosen by the tag, never by the size.
+struct f16_t {
+  uint16_t bits;
+  f16_t() = default;
+  __host__ __device__ constexpr explicit f16_t(uint16_t b) : bits(b) {}
+};
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+
+// round-to-nearest-even f32 -> f16 bits (v_cvt_f16_f32) and back (exact)
+__device__ __forceinline__ uint16_t f2h(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
+__device__ __forceinline__ float h2f(uint16_t x) { return (float)__builtin_bit_cast(_Float16, x); }
+
 // S^T / O^T accumulator row for register r of lane-half h.
 __device__ __forceinline__ constexpr int acc_row(int r, int h) {
   return (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -70,6 +83,41 @@ struct MmaBf16 {
     frag f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) f.v[j] = (short)f2bf(p[j]);
+    return f;
+  }
+};
+
+// f16 operands, f32 accumulate: the PV product of fp16 inputs.  V is staged as the raw f16 bits
+// (vt_frag's transposing LDS read is type-agnostic for 16-bit data) and P is packed to f16 with
+// round-to-nearest: p <= 2^8 under the defer-max rule (far inside the f16 range), 11 significant
+// bits where bf16 keeps 8.  Kernels that let p grow with the f32 exponent range (the NOMAX loops)
+// must not be instantiated with this trait.
+struct MmaF16 {
+  using elem = f16_t;
+  struct frag {
+    short8_t v;
+  };
+  static constexpr int kElemBytes = 2;
+
+  __device__ __forceinline__ static void mma(f32x16_t& acc, const frag& a, const frag& b) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a.v),
+                                                 __builtin_bit_cast(f16x8_t, b.v), acc, 0, 0, 0);
+  }
+  __device__ __forceinline__ static elem from_float(float x) { return f16_t(f2h(x)); }
+  __device__ __forceinline__ static frag load8(const elem* p) {
+    frag f;
+    f.v = *reinterpret_cast<const short8_t*>(p);
+    return f;
+  }
+  __device__ __forceinline__ static frag zero() {
+    frag f;
+    f.v = short8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    return f;
+  }
+  __device__ __forceinline__ static frag pack_p(const float* p) {
+    frag f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f.v[j] = (short)f2h(p[j]);
     return f;
   }
 };
@@ -176,6 +224,23 @@ struct Chunk8<uint16_t> {
   }
 };
 
+// fp16 tensors: the raw bits travel unconverted (staging, Q fragments); only a store into an f32
+// image widens them.
+template <>
+struct Chunk8<f16_t> {
+  short8_t v;
+  __device__ __forceinline__ void load(const f16_t* src) { v = *reinterpret_cast<const short8_t*>(src); }
+  __device__ __forceinline__ void load_buf(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+    v = __builtin_bit_cast(short8_t, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+  }
+  __device__ __forceinline__ void clear() { v = short8_t{0, 0, 0, 0, 0, 0, 0, 0}; }
+  __device__ __forceinline__ void store(f16_t* dst) const { *reinterpret_cast<short8_t*>(dst) = v; }
+  __device__ __forceinline__ void store(float* dst) const {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dst[j] = h2f((uint16_t)v[j]);
+  }
+};
+
 // ------------------------------------------------------------------ QK^T precision traits
 // How S^T = K Q^T is formed.  K tiles live in LDS in `planes` planes of [rows][KS] elements
 // (plane stride passed at the call site); Q fragments stay in registers.
@@ -208,6 +273,29 @@ struct QkBf16 {
   __device__ __forceinline__ static void mma(f32x16_t& acc, const frag& k, const frag& q) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, k.h),
                                                   __builtin_bit_cast(bf16x8_t, q.h), acc, 0, 0, 0);
+  }
+};
+
+//   QkF16    : fp16 inputs, K staged as the raw f16 bits, one f16 MFMA per 16-deep k step (an
+//              11-bit x 11-bit product is exact in the f32 accumulator)
+struct QkF16 {
+  using elem = f16_t;
+  static constexpr int planes = 1;
+  static constexpr int kElemBytes = 2;
+  struct frag {
+    short8_t h;
+  };
+  __device__ __forceinline__ static frag zero() { return frag{short8_t{0, 0, 0, 0, 0, 0, 0, 0}}; }
+  __device__ __forceinline__ static frag load_k(const elem* p, int) {
+    return frag{*reinterpret_cast<const short8_t*>(p)};
+  }
+  __device__ __forceinline__ static frag load_q(const f16_t* src) {
+    return frag{*reinterpret_cast<const short8_t*>(src)};
+  }
+  __device__ __forceinline__ static void stage(const Chunk8<f16_t>& c, elem* dst, int) { c.store(dst); }
+  __device__ __forceinline__ static void mma(f32x16_t& acc, const frag& k, const frag& q) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, k.h),
+                                                 __builtin_bit_cast(f16x8_t, q.h), acc, 0, 0, 0);
   }
 };
 
@@ -285,6 +373,26 @@ __device__ __forceinline__ void store4(uint16_t* dst, float a, float b, float c,
   v[0] = (short)f2bf(a); v[1] = (short)f2bf(b); v[2] = (short)f2bf(c); v[3] = (short)f2bf(d);
   *reinterpret_cast<short4_t*>(dst) = v;
 }
+__device__ __forceinline__ void store4(f16_t* dst, float a, float b, float c, float d) {
+  short4_t v;
+  v[0] = (short)f2h(a); v[1] = (short)f2h(b); v[2] = (short)f2h(c); v[3] = (short)f2h(d);
+  *reinterpret_cast<short4_t*>(dst) = v;
+}
+
+// 16-bit I/O element tags (bf16 or fp16): what the raw-bit paths (buffer-load staging, the LDS
+// output transpose) may be used for; anything that converts asks for the exact tag instead.
+template <typename IO>
+struct is_io16 {
+  static constexpr bool value = false;
+};
+template <>
+struct is_io16<uint16_t> {
+  static constexpr bool value = true;
+};
+template <>
+struct is_io16<f16_t> {
+  static constexpr bool value = true;
+};
 
 // AttentionStore read-add-write of one wave's [rows][K] block of post-edit maps: g (16-byte
 // aligned, cnt = rows * K floats, cnt % 4 == 0) (+)= slab (the wave's LDS copy of the rows).
@@ -374,6 +482,23 @@ __device__ __forceinline__ void pv_block(MmaBf16, f32x16_t (&O)[NDT], const uint
     for (int dt = 0; dt < NDT; ++dt) {
       const MmaBf16::frag a = vt_frag<VS>(V, row0, s, dt * 32, lane);
       MmaBf16::mma(O[dt], a, b);
+    }
+  }
+}
+
+// The same for fp16 inputs: V's raw f16 image through the same transposing reads (16-bit data,
+// whatever its format), P packed to f16, f16 MFMA.
+template <int VS, int NDT>
+__device__ __forceinline__ void pv_block(MmaF16, f32x16_t (&O)[NDT], const f16_t* V, int row0,
+                                         const float (&p)[16], int lane) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const MmaF16::frag b = MmaF16::pack_p(p + 8 * s);
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+      MmaF16::frag a;
+      a.v = vt_frag<VS>(reinterpret_cast<const uint16_t*>(V), row0, s, dt * 32, lane).v;
+      MmaF16::mma(O[dt], a, b);
     }
   }
 }

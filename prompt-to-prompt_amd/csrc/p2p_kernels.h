@@ -103,10 +103,10 @@ int run_cross(const CrossArgs& a, int io_dtype, int compute, int d, hipStream_t 
 // group-coupled cross-attention (p2p_cross.hip): bf16 inputs and compute, dense or no programs
 bool cross_group_eligible(const CrossArgs& a, int d);
 int run_cross_group(const CrossArgs& a, int d, hipStream_t st);
-// d = 40 / 80 self-attention with bf16 inputs, O only (p2p_self40.hip): the G1/G7 and G2/G6
-// production kernels
+// d = 40 / 80 self-attention with bf16 (or, f16_inputs, fp16) inputs, O only (p2p_self40.hip): the
+// G1/G7 and G2/G6 production kernels
 bool self40_eligible(const SelfArgs& a, int d);
-int run_self40(const SelfArgs& a, int d, hipStream_t st);
+int run_self40(const SelfArgs& a, int d, hipStream_t st, bool f16_inputs = false);
 // d = 160 self-attention with bf16 inputs, O only, K <= 256 (p2p_selfsplit.hip): key-split waves
 bool self_split_eligible(const SelfArgs& a, int d);
 int run_self_split(const SelfArgs& a, int d, hipStream_t st);

@@ -21,6 +21,17 @@
 // the f16 range, |m| >= 65504, a non-finite row sum or O element -- flags the workgroup, which
 // recomputes everything on the exact bf16 path (unscaled bf16 Q and K, running max per
 // sub-block).
+//
+// fp16 inputs (H16): the same pipeline with f16 operands throughout.  d = 40: Q prescaled by c and
+// rounded to f16 as above (|c q| < 65504 always: c < 1), K copied to LDS unconverted -- no
+// conversion, no range check --, the -m column as above; d = 80: raw f16 Q and K on the f16 MFMA.
+// V's ones column is f16 1.0, P is packed to f16 (v_cvt_pkrtz: the row sum is the sum of the same
+// rounded p) and P V runs on the f16 MFMA.  f16 P has 5 exponent bits where bf16 has 8, so the
+// row sum is held below 2^15 instead of 2^64: a tile that leaves it in [2^14, 2^15) moves m up by
+// 8, one that leaves it at 2^15 or more (some p may have been clamped at 65504) sends the
+// workgroup to the exact recompute, which runs on the raw f16 Q and K.  m is a logit of the row,
+// so the row sum is >= 1 and the f16 subnormals among the p (< 2^-14, absolute error < 2^-24
+// each) stay below K 2^-24 of it.  The epilogue rounds O to f16.
 #include <type_traits>
 #include <utility>
 
@@ -94,7 +105,7 @@ __device__ unsigned long long g_s40_stamps[kStampWgs * 8 * kStampSlots];
 //   128      split staging: waves 0..WAVES/2-1 stage K (the f16 conversion), the rest V
 //   256/512/16384  the younger half holds priority 1 for 3 of every 4 steps
 //   8388608  K's f16 range check as a packed-u16 maximum
-template <int kD, int WAVES, int QB, int BK, bool SCHED, int FORM>
+template <int kD, int WAVES, int QB, int BK, bool SCHED, int FORM, bool H16 = false>
 __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(SelfArgs a) {
   using G = Geom<kD>;
   constexpr bool kF16 = G::F16;
@@ -177,7 +188,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
   const uint16_t* const vp = static_cast<const uint16_t*>(a.v) + (int64_t)n * a.bsv + h * kD;
 
   // padding columns (written once; staging writes columns 0..D-1 only): F16 K column D = f16 1.0
-  // (the -m column), D+1..DK-1 = 0; V column D = bf16 1.0 (row sums), D+1..DV-1 = 0
+  // (the -m column), D+1..DK-1 = 0; V column D = 1.0 in V's format (row sums), D+1..DV-1 = 0
   for (int r = tid; r < 2 * BK; r += NT) {
 #pragma unroll
     for (int j = 0; j < (kDK - kD) / 8; ++j)
@@ -186,7 +197,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
 #pragma unroll
     for (int j = 0; j < (kDV - kD) / 8; ++j)
       *reinterpret_cast<short8_t*>(Vs + r * kVS + kD + 8 * j) =
-          short8_t{(short)(j == 0 ? 0x3F80 : 0), 0, 0, 0, 0, 0, 0, 0};
+          short8_t{(short)(j == 0 ? (H16 ? 0x3C00 : 0x3F80) : 0), 0, 0, 0, 0, 0, 0, 0};
   }
   if (tid == 0) wg_flag = 0;
 
@@ -218,11 +229,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
           float mx = 0.f;
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            const float x = bf2f((uint16_t)v[j]) * c;
+            const float x = (H16 ? h2f((uint16_t)v[j]) : bf2f((uint16_t)v[j])) * c;
             mx = fmaxf(mx, fabsf(x));
             v[j] = (short)__builtin_bit_cast(uint16_t, (_Float16)x);
           }
-          ovf |= !(mx < 65520.f);
+          if constexpr (!H16) ovf |= !(mx < 65520.f);   // (fp16 inputs: |c q| < 65504, c < 1)
         }
         qf[b][t] = v;
       }
@@ -285,7 +296,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
       return;
     }
     uint16_t* const kd = Ks + buf * KBUF + lrow[i] * kKS + lch[i] * 8;
-    if (as_f16 && kU16Max) {
+    if (H16 || !as_f16) {   // raw bf16 (exact path), or fp16 inputs: K is f16 already
+      *reinterpret_cast<short8_t*>(kd) = kreg[i];
+    } else if (kU16Max) {
       const u32x4_t wv = __builtin_bit_cast(u32x4_t, kreg[i]);
       u32x4_t hv;
 #pragma unroll
@@ -296,7 +309,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
                                                                        __uint_as_float(w & 0xffff0000u)));
       }
       *reinterpret_cast<u32x4_t*>(kd) = hv;
-    } else if (as_f16) {
+    } else {
       short8_t hv;
       float mx = 0.f;
 #pragma unroll
@@ -309,8 +322,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
       }
       ovf |= !(mx < 65504.f);
       *reinterpret_cast<short8_t*>(kd) = hv;
-    } else {
-      *reinterpret_cast<short8_t*>(kd) = kreg[i];
     }
     if constexpr (kRole == 0) *reinterpret_cast<short8_t*>(Vs + buf * VBUF + lrow[i] * kVS + lch[i] * 8) = vreg[i];
   };
@@ -359,7 +370,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
       f32x16_t acc = f32x16_t{};
 #pragma unroll
       for (int t = 0; t < kNKT; ++t) {
-        if constexpr (kF16) mma_f16(acc, kf[t], qf[b][t]);
+        if constexpr (kF16 || H16) mma_f16(acc, kf[t], qf[b][t]);
         else mma_bf16(acc, kf[t], qf[b][t]);
       }
       float mx = -INFINITY;
@@ -404,7 +415,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
       S[x & 1] = f32x16_t{};
 #pragma unroll
       for (int t = 0; t < kNKT; ++t) {
-        if constexpr (kF16) mma_f16(S[x & 1], kf[kslot(sb)][t], qf[b][t]);
+        if constexpr (kF16 || H16) mma_f16(S[x & 1], kf[kslot(sb)][t], qf[b][t]);
         else mma_bf16(S[x & 1], kf[kslot(sb)][t], qf[b][t]);
       }
     };
@@ -413,7 +424,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int dt = 0; dt < kNDT; ++dt) mma_bf16(O[b][dt], vf[vslot(sb)][s2][dt], pf[x & 1][s2]);
+        for (int dt = 0; dt < kNDT; ++dt) {
+          if constexpr (H16) mma_f16(O[b][dt], vf[vslot(sb)][s2][dt], pf[x & 1][s2]);
+          else mma_bf16(O[b][dt], vf[vslot(sb)][s2][dt], pf[x & 1][s2]);
+        }
     };
     auto ex = [&](int x) __attribute__((always_inline)) {
       const int sb = x / QB, b = x % QB;
@@ -428,7 +442,16 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) pf[x & 1][s2][j] = (short)f2bf(e[8 * s2 + j]);
+        for (int j = 0; j < 8; j += 2) {
+          if constexpr (H16) {
+            const auto pk = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(e[8 * s2 + j], e[8 * s2 + j + 1]));
+            pf[x & 1][s2][j] = (short)(pk & 0xffff);
+            pf[x & 1][s2][j + 1] = (short)(pk >> 16);
+          } else {
+            pf[x & 1][s2][j] = (short)f2bf(e[8 * s2 + j]);
+            pf[x & 1][s2][j + 1] = (short)f2bf(e[8 * s2 + j + 1]);
+          }
+        }
     };
     qk(0);
     if constexpr (SCHED) __builtin_amdgcn_sched_barrier(0);
@@ -479,7 +502,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
         constexpr int nq = x + 1 < X ? kNKT : 0;
         constexpr int nm = nq + (x >= 1 ? 2 * kNDT : 0);
         constexpr int ne = 16;
-        constexpr int nv = 8 + (kF16 ? 0 : 16) + (kStwK && kF16 ? 24 * (c1 - c0) : 0) + (kMasked ? 32 : 0);
+        constexpr int nv = 8 + (kF16 ? 0 : 16) + (kStwK && kF16 && !H16 ? 24 * (c1 - c0) : 0) + (kMasked ? 32 : 0);
         constexpr int nr = (!kLeanK && kRdK ? kNKT : 0) + (!kLean && kRdV ? 4 * kNDT : 0);
         if constexpr (kRdKEarly) __builtin_amdgcn_sched_group_barrier(0x100, kNKT, 0);
         static_for<nm>([&](auto ic) __attribute__((always_inline)) {
@@ -518,11 +541,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
       const float lsum = lsums[b];
-      bad |= !(lsum < INFINITY);
-      constexpr float kResc = 0x1p64f;
+      // (fp16 inputs: f16 P -- a sum of 2^15 or more may hold a p clamped at 65504: exact recompute;
+      // in [2^14, 2^15) no p was clamped and m moves up by 8)
+      bad |= !(lsum < (H16 ? 0x1p15f : INFINITY));
+      constexpr float kResc = H16 ? 0x1p14f : 0x1p64f;
+      constexpr float kUp = H16 ? 8.f : 64.f;
       if (__builtin_expect(__any(lsum > kResc), 0)) {
         if (lsum > kResc) {
-          const float mnew = kF16 ? (float)(_Float16)(m_ref[b] + 64.f) : m_ref[b] + 64.f;
+          const float mnew = kF16 ? (float)(_Float16)(m_ref[b] + kUp) : m_ref[b] + kUp;
           ovf |= !(fabsf(mnew) < (kF16 ? 65504.f : INFINITY));
           const float f = fast_exp2(m_ref[b] - mnew);
 #pragma unroll
@@ -565,8 +591,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
   }
   __syncthreads();
   if (__builtin_expect(wg_flag != 0, 0)) {
-    // ---- exact recompute: bf16 Q and K as they are, S = Q K^T in f32, running max per
-    // 32-key sub-block with the defer-max rule (the sub-block's P V follows at once)
+    // ---- exact recompute: bf16 (fp16) Q and K as they are, S = Q K^T in f32, running max per
+    // 32-key sub-block with the defer-max rule (the sub-block's P V follows at once; p <= 2^8)
     load_q(false);
     float m_run[QB];
 #pragma unroll
@@ -587,7 +613,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
         for (int b = 0; b < QB; ++b) {
           f32x16_t acc = f32x16_t{};
 #pragma unroll
-          for (int t = 0; t < kNKT; ++t) mma_bf16(acc, kf[t], qf[b][t]);
+          for (int t = 0; t < kNKT; ++t) {
+            if constexpr (H16) mma_f16(acc, kf[t], qf[b][t]);
+            else mma_bf16(acc, kf[t], qf[b][t]);
+          }
           float sv[16];
           float mx = -INFINITY;
 #pragma unroll
@@ -607,11 +636,17 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
           }
           short8_t pb[2];
 #pragma unroll
-          for (int r = 0; r < 16; ++r) pb[r >> 3][r & 7] = (short)f2bf(fast_exp2(sv[r] - m_run[b]));
+          for (int r = 0; r < 16; ++r) {
+            const float e = fast_exp2(sv[r] - m_run[b]);
+            pb[r >> 3][r & 7] = (short)(H16 ? f2h(e) : f2bf(e));
+          }
 #pragma unroll
           for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-            for (int dt = 0; dt < kNDT; ++dt) mma_bf16(O[b][dt], vf[s2][dt], pb[s2]);
+            for (int dt = 0; dt < kNDT; ++dt) {
+              if constexpr (H16) mma_f16(O[b][dt], vf[s2][dt], pb[s2]);
+              else mma_bf16(O[b][dt], vf[s2][dt], pb[s2]);
+            }
         }
       }
       __syncthreads();
@@ -633,9 +668,15 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int dd = dt * 32 + 8 * g + 4 * hh;
-        if (dd < kD)
-          store4(orow + (32 * b + qi) * kOS + dd, O[b][dt][4 * g] * inv, O[b][dt][4 * g + 1] * inv,
-                 O[b][dt][4 * g + 2] * inv, O[b][dt][4 * g + 3] * inv);
+        if (dd < kD) {
+          uint16_t* const od = orow + (32 * b + qi) * kOS + dd;
+          if constexpr (H16)
+            store4(reinterpret_cast<f16_t*>(od), O[b][dt][4 * g] * inv, O[b][dt][4 * g + 1] * inv,
+                   O[b][dt][4 * g + 2] * inv, O[b][dt][4 * g + 3] * inv);
+          else
+            store4(od, O[b][dt][4 * g] * inv, O[b][dt][4 * g + 1] * inv, O[b][dt][4 * g + 2] * inv,
+                   O[b][dt][4 * g + 3] * inv);
+        }
       }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -657,12 +698,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
   stamp(37);
 }
 
-template <int D, int WAVES, int QB, int BK, bool SCHED = true, int FORM = 0>
+template <int D, int WAVES, int QB, int BK, bool SCHED = true, int FORM = 0, bool H16 = false>
 hipError_t launch(const SelfArgs& a, hipStream_t st) {
   SelfArgs b = a;
   b.n_qtiles = (a.P + 32 * QB * WAVES - 1) / (32 * QB * WAVES);
   dim3 grid(b.n_qtiles * a.H * a.N), block(64 * WAVES);
-  launch_kernel((self40_kernel<D, WAVES, QB, BK, SCHED, FORM>), grid, block, 0, st, b);
+  launch_kernel((self40_kernel<D, WAVES, QB, BK, SCHED, FORM, H16>), grid, block, 0, st, b);
   return hipGetLastError();
 }
 
@@ -676,10 +717,16 @@ bool self40_eligible(const SelfArgs& a, int d) {
 
 // variant: 0 = production shapes; the experiments build also honours the A/B shapes below
 // (every other measured shape is in git history; DESIGN.md §4 and profiles/ hold the logs)
-int run_self40(const SelfArgs& a, int d, hipStream_t st) {
+int run_self40(const SelfArgs& a, int d, hipStream_t st, bool f16_inputs) {
 #ifdef S40_ONLY
   return (int)launch<S40_ONLY>(a, st);
 #else
+  // fp16 inputs: the launch shapes of the bf16 defaults below (K's packed-u16 range check has
+  // nothing to check)
+  if (f16_inputs) {
+    if (d == 80) return (int)launch<80, 8, 1, 128, true, 1 | 128 | 256 | 512 | 16384, true>(a, st);
+    return (int)launch<40, 8, 2, 256, true, 1 | 128 | 256 | 512 | 16384, true>(a, st);
+  }
   if (d == 80) {
     switch (a.variant) {
 #ifdef P2P_EXPERIMENTS

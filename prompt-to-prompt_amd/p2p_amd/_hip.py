@@ -25,6 +25,7 @@ LAUNCH_OBSERVER = None
 
 P2P_DTYPE_F32 = 0
 P2P_DTYPE_BF16 = 1
+P2P_DTYPE_F16 = 2
 P2P_COMPUTE_BF16 = 0
 P2P_COMPUTE_F32 = 1
 MAX_BATCH = 64
@@ -32,7 +33,7 @@ MAX_GROUPS = 32
 MAX_KEYS_CROSS = 96
 PROGRAM_COLS = 128
 PROGRAM_TMAX = 8
-ABI_VERSION = 15
+ABI_VERSION = 16
 GROUP_F_R_ONLY = 2      # p2p_group.flags: every edit's blend coefficient A is 0 this call (P' = R)
 GROUP_F_SHARED_KV = 4   # p2p_group.flags: every entry of the group has the first entry's K and V
 
@@ -173,7 +174,9 @@ def _dtype_code(t: torch.Tensor) -> int:
         return P2P_DTYPE_F32
     if t.dtype == torch.bfloat16:
         return P2P_DTYPE_BF16
-    raise HipError(f"unsupported attention dtype {t.dtype} (float32 or bfloat16)")
+    if t.dtype == torch.float16:
+        return P2P_DTYPE_F16
+    raise HipError(f"unsupported attention dtype {t.dtype} (float32, bfloat16 or float16)")
 
 
 _COMPUTE = {"bf16": P2P_COMPUTE_BF16, "f32": P2P_COMPUTE_F32}
@@ -394,7 +397,7 @@ def store_scale(src: torch.Tensor, divisor: float, out: Optional[torch.Tensor] =
 
 def latent_step(eps, x, out, coeffs, guidance=None, mask=None, group_size=0, group_blend=None, blend=None):
     """Fused CFG + DDIM step + LocalBlend blend (p2p_latent_step).  eps: [2B or B, C, H, W]
-    (f32/bf16, uncond block first when guidance is given); x, out: f32 [B, C, H, W] (out may be
+    (f32/bf16/f16, uncond block first when guidance is given); x, out: f32 [B, C, H, W] (out may be
     x unless ``blend`` is given); coeffs: (sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev,
     sqrt_one_minus_alpha_prev) floats; mask: uint8 [B, H, W] or None; group_size: prompts per
     prompt group (0 = one group), with group_blend (uint8 [B / group_size] or None = every group)

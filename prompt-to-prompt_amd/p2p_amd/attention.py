@@ -47,6 +47,10 @@ class _AttentionFn(torch.autograd.Function):
 def differentiable_attention(q, k, v, heads, scale):
     if config.COMPUTE != "bf16":
         raise NotImplementedError("the attention backward runs on the bf16 kernels only (compute='bf16')")
+    if torch.float16 in (q.dtype, k.dtype, v.dtype):
+        # the backward kernels read 16-bit tensors as bf16: refused here, before any launch
+        raise NotImplementedError("the attention backward takes float32 or bfloat16 tensors, not float16 "
+                                  "(run the differentiated U-Net in bfloat16 or float32)")
     return _AttentionFn.apply(q, k, v, heads, scale)
 
 

@@ -47,7 +47,7 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
     from . import _hip
     from .ddim import DDIMScheduler
     if not (isinstance(model.scheduler, DDIMScheduler) and latents.is_cuda and latents.dtype == torch.float32
-            and eps_u.dtype in (torch.float32, torch.bfloat16) and hasattr(controller, "fused_step_mask")):
+            and eps_u.dtype in (torch.float32, torch.bfloat16, torch.float16) and hasattr(controller, "fused_step_mask")):
         return None
     ok, mask_fn = controller.fused_step_mask()
     if not ok:
