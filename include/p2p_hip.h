@@ -257,6 +257,65 @@ int p2p_latent_step(const p2p_latent_step_args* a, p2p_stream_t stream);
  * reference's cuda:0 device. */
 int p2p_store_scale(const float* src, float* dst, float divisor, int64_t n, p2p_stream_t stream);
 
+/* U-Net glue between the convolutions and GEMMs (p2p_amd/unet.py; additive to ABI 16): 16-bit
+ * tensors only (dtype = P2P_DTYPE_BF16 or P2P_DTYPE_F16, anything else is P2P_E_DTYPE), f32
+ * arithmetic, one rounding at the store, fixed-order reductions (bit-identical from launch to
+ * launch).  Tensors are dense; x / y / a / b / out pointers are 16-byte aligned and hw % 8 == 0
+ * (token-major tensors also need channels % 8 == 0), else P2P_E_ALIGN. */
+enum { P2P_ACT_NONE = 0, P2P_ACT_SILU = 1 };
+enum { P2P_LAYOUT_NCHW = 0,    /* [n, channels, hw]                                         */
+       P2P_LAYOUT_TOKENS = 1   /* [n, hw, channels] (the transformer blocks' token layout)  */ };
+
+/* y = act(GroupNorm(x + chan_add + chan_bias) * gamma + beta): nn.GroupNorm (+ F.silu) with the
+ * per-channel adds in front of it (ResnetBlock2D: conv1's bias and the time-embedding projection)
+ * taken on load.  Statistics per (n, group): mean, then the centred variance (biased, as torch),
+ * both f32.  x is NCHW; y is NCHW or token-major. */
+typedef struct {
+  const void* x;            /* [n, channels, hw]                                           */
+  const void* chan_add;     /* nullable: [n, channels] (stride = channels) or [channels] (0) */
+  int64_t chan_add_stride;  /* 0 or channels                                                */
+  const void* chan_bias;    /* nullable [channels], added like chan_add                     */
+  const void* gamma;        /* [channels]                                                   */
+  const void* beta;         /* [channels]                                                   */
+  void* y;
+  float* stats;             /* workspace [n * groups * 2] f32 ({mean, rstd} per slab)       */
+  int32_t n, channels, hw, groups;
+  float eps;
+  int32_t act;              /* P2P_ACT_*                                                    */
+  int32_t y_layout;         /* P2P_LAYOUT_*                                                 */
+  int32_t dtype;            /* P2P_DTYPE_BF16 / P2P_DTYPE_F16: every tensor but stats       */
+} p2p_group_norm_args;
+
+int p2p_group_norm(const p2p_group_norm_args* a, p2p_stream_t stream);
+
+/* out[n, c, hw] = a[n, c, hw] + b + bias[c] + bias2[c]: the residual add of ResnetBlock2D with the
+ * biases of conv2 and of the shortcut conv (b NCHW), and of Transformer2DModel (b = the proj_out
+ * tokens, token-major).  a and out are NCHW (out may be a); the biases are nullable. */
+typedef struct {
+  const void* a;
+  const void* b;
+  const void* bias;   /* nullable [channels] */
+  const void* bias2;  /* nullable [channels] */
+  void* out;
+  int32_t n, channels, hw;
+  int32_t b_layout;   /* P2P_LAYOUT_* */
+  int32_t dtype;
+} p2p_bias_residual_args;
+
+int p2p_bias_residual(const p2p_bias_residual_args* a, p2p_stream_t stream);
+
+/* GEGLU: out[m, j] = in[m, j] * gelu(in[m, d + j]), j < d, gelu the exact erf form (F.gelu's
+ * default).  Row strides in elements, multiples of 8 (as d), in_row_stride >= 2 d. */
+typedef struct {
+  const void* in;
+  void* out;
+  int64_t in_row_stride, out_row_stride;
+  int32_t rows, d;
+  int32_t dtype;
+} p2p_geglu_args;
+
+int p2p_geglu(const p2p_geglu_args* a, p2p_stream_t stream);
+
 /* Measurement only (ABI 15; bench.py's roofline clock, not part of the reference's interface):
  * n_workgroups one-wave workgroups each read the shader-cycle counter and the constant 100 MHz
  * counter, spin until `ticks` (1..1e6) of the 100 MHz counter have passed, and read both again:

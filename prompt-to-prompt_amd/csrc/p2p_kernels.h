@@ -134,6 +134,11 @@ struct BwdArgs {
 int run_attn_bwd(const BwdArgs& a, int io_dtype, int d, hipStream_t st);
 int bwd_kv_split(int N, int H, int P, int K, int d);   // launcher's query split (workspace sizing)
 int run_store_scale(const float* src, float* dst, float divisor, int64_t n, hipStream_t st);
+// U-Net glue (p2p_unet.hip): every argument check happens in these, before the first launch
+constexpr int64_t kGnStatsWide = 32768;   // slab elements from which the statistics kernel runs 1024 threads
+int run_group_norm(const p2p_group_norm_args& a, hipStream_t st);
+int run_bias_residual(const p2p_bias_residual_args& a, hipStream_t st);
+int run_geglu(const p2p_geglu_args& a, hipStream_t st);
 int run_clock_probe(unsigned long long* out, int n_wg, int ticks, hipStream_t st);
 
 }  // namespace p2p

@@ -1,7 +1,9 @@
 """ctypes binding of ``libp2p_hip.so`` (C ABI: ``include/p2p_hip.h``).
 
 This module is the only place the product talks to the device kernels.  There is no
-fallback: if the shared library is missing or a call is rejected, it raises.
+fallback: if the shared library is missing or a call is rejected, it raises.  (The U-Net glue
+functions at the end report a dtype or alignment the kernels do not take as None, so that the
+module keeps its torch lines for f32 and odd shapes; everything else they are refused raises too.)
 """
 from __future__ import annotations
 
@@ -88,6 +90,31 @@ class LatentArgs(ctypes.Structure):
     ]
 
 
+class GroupNormArgs(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("chan_add", ctypes.c_void_p), ("chan_add_stride", ctypes.c_int64),
+        ("chan_bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+        ("y", ctypes.c_void_p), ("stats", ctypes.c_void_p),
+        ("n", ctypes.c_int32), ("channels", ctypes.c_int32), ("hw", ctypes.c_int32), ("groups", ctypes.c_int32),
+        ("eps", ctypes.c_float), ("act", ctypes.c_int32), ("y_layout", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
+class BiasResidualArgs(ctypes.Structure):
+    _fields_ = [
+        ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("bias2", ctypes.c_void_p),
+        ("out", ctypes.c_void_p), ("n", ctypes.c_int32), ("channels", ctypes.c_int32), ("hw", ctypes.c_int32),
+        ("b_layout", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
+class GegluArgs(ctypes.Structure):
+    _fields_ = [
+        ("inp", ctypes.c_void_p), ("out", ctypes.c_void_p), ("in_row_stride", ctypes.c_int64),
+        ("out_row_stride", ctypes.c_int64), ("rows", ctypes.c_int32), ("d", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -115,11 +142,14 @@ def lib():
         L.p2p_attn_bwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
         L.p2p_attn_bwd_workspace.argtypes = [ctypes.POINTER(AttnTensors)]
         L.p2p_attn_bwd_workspace.restype = ctypes.c_int64
+        L.p2p_group_norm.argtypes = [ctypes.POINTER(GroupNormArgs), vp]
+        L.p2p_bias_residual.argtypes = [ctypes.POINTER(BiasResidualArgs), vp]
+        L.p2p_geglu.argtypes = [ctypes.POINTER(GegluArgs), vp]
         L.p2p_clock_probe.argtypes = [vp, i32, i32, vp]
         L.p2p_set_launch_events.argtypes = [vp, vp]
         for fn in ("p2p_self_attn_fwd", "p2p_cross_attn_fwd", "p2p_attn_probs", "p2p_attn_pv",
                    "p2p_localblend", "p2p_store_scale", "p2p_latent_step", "p2p_attn_fwd_lse", "p2p_attn_bwd",
-                   "p2p_clock_probe", "p2p_set_launch_events"):
+                   "p2p_clock_probe", "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu"):
             getattr(L, fn).restype = ctypes.c_int
         if L.p2p_abi_version() != ABI_VERSION:
             raise HipError(f"libp2p_hip.so ABI {L.p2p_abi_version()} != {ABI_VERSION}")
@@ -145,7 +175,7 @@ def check_source_hash() -> str:
 EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p2p_self_attn_fwd", "p2p_cross_attn_fwd",
                     "p2p_attn_probs", "p2p_attn_pv", "p2p_localblend", "p2p_store_scale", "p2p_latent_step",
                     "p2p_attn_fwd_lse", "p2p_attn_bwd", "p2p_attn_bwd_workspace", "p2p_clock_probe",
-                    "p2p_set_launch_events")
+                    "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -490,3 +520,99 @@ def attn_bwd(q, k, v, o, dout, lse, heads, scale, dq, dk, dv, delta, workspace=N
     rc = lib().p2p_attn_bwd(ctypes.byref(t), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(),
                             dk.data_ptr(), dv.data_ptr(), kv_f32, ws_ptr, need, _stream(q.device))
     _check(rc, "p2p_attn_bwd")
+
+
+# -- U-Net glue (p2p_unet.hip).  Each returns its output, or None when the library reports the
+# arguments unsupported (dtype, alignment) or the tensors are not dense: the caller then runs
+# its torch lines.  Any other rejection raises.
+P2P_E_DTYPE, P2P_E_ALIGN = -3, -6
+ACT_NONE, ACT_SILU = 0, 1
+LAYOUT_NCHW, LAYOUT_TOKENS = 0, 1
+
+
+def _glue_rc(rc: int, what: str) -> bool:
+    if rc in (P2P_E_DTYPE, P2P_E_ALIGN):
+        return False
+    _check(rc, what)
+    return True
+
+
+def _glue_dtype(t: torch.Tensor) -> int:
+    return {torch.bfloat16: P2P_DTYPE_BF16, torch.float16: P2P_DTYPE_F16}.get(t.dtype, P2P_DTYPE_F32)
+
+
+def _vec(t: Optional[torch.Tensor], like: torch.Tensor, numel: int):
+    """A dense per-channel vector in ``like``'s dtype (or None)."""
+    if t is None:
+        return None
+    if t.dtype != like.dtype or not t.is_contiguous() or t.numel() != numel:
+        raise HipError("per-channel operand must be dense, in the tensor's dtype")
+    return t
+
+
+def group_norm(x, gamma, beta, groups: int, eps: float, silu: bool = False, tokens: bool = False,
+               chan_add=None, chan_bias=None):
+    """act(GroupNorm(x + chan_add + chan_bias) * gamma + beta) (p2p_group_norm).  x: [N, C, H, W];
+    chan_add: [N, C] or [C]; chan_bias: [C]; returns [N, C, H, W], or [N, H*W, C] with ``tokens``."""
+    _require_cuda(x, gamma, beta, chan_add, chan_bias)
+    if x.dim() != 4 or not x.is_contiguous():
+        return None
+    N, C, H, W = x.shape
+    a = GroupNormArgs()
+    a.x = x.data_ptr()
+    if chan_add is not None:
+        per_n = chan_add.dim() == 2
+        _vec(chan_add, x, N * C if per_n else C)
+        a.chan_add, a.chan_add_stride = chan_add.data_ptr(), C if per_n else 0
+    if chan_bias is not None:
+        a.chan_bias = _vec(chan_bias, x, C).data_ptr()
+    a.gamma, a.beta = _vec(gamma, x, C).data_ptr(), _vec(beta, x, C).data_ptr()
+    y = x.new_empty((N, H * W, C) if tokens else (N, C, H, W))
+    stats = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
+    a.y, a.stats = y.data_ptr(), stats.data_ptr()
+    a.n, a.channels, a.hw, a.groups = N, C, H * W, int(groups)
+    a.eps = float(eps)
+    a.act = ACT_SILU if silu else ACT_NONE
+    a.y_layout = LAYOUT_TOKENS if tokens else LAYOUT_NCHW
+    a.dtype = _glue_dtype(x)
+    return y if _glue_rc(lib().p2p_group_norm(ctypes.byref(a), _stream(x.device)), "p2p_group_norm") else None
+
+
+def bias_residual(a_nchw, b, bias=None, bias2=None, tokens: bool = False):
+    """a + b + bias + bias2 as [N, C, H, W] (p2p_bias_residual).  a_nchw: [N, C, H, W]; b: the same
+    shape, or [N, H*W, C] with ``tokens``; biases: [C] or None."""
+    _require_cuda(a_nchw, b, bias, bias2)
+    if a_nchw.dim() != 4 or not a_nchw.is_contiguous() or not b.is_contiguous() or b.dtype != a_nchw.dtype:
+        return None
+    N, C, H, W = a_nchw.shape
+    if tuple(b.shape) != ((N, H * W, C) if tokens else (N, C, H, W)):
+        raise HipError(f"bias_residual: b {tuple(b.shape)} does not match a {tuple(a_nchw.shape)}")
+    r = BiasResidualArgs()
+    r.a, r.b = a_nchw.data_ptr(), b.data_ptr()
+    if bias is not None:
+        r.bias = _vec(bias, a_nchw, C).data_ptr()
+    if bias2 is not None:
+        r.bias2 = _vec(bias2, a_nchw, C).data_ptr()
+    out = torch.empty_like(a_nchw)
+    r.out = out.data_ptr()
+    r.n, r.channels, r.hw = N, C, H * W
+    r.b_layout = LAYOUT_TOKENS if tokens else LAYOUT_NCHW
+    r.dtype = _glue_dtype(a_nchw)
+    ok = _glue_rc(lib().p2p_bias_residual(ctypes.byref(r), _stream(a_nchw.device)), "p2p_bias_residual")
+    return out if ok else None
+
+
+def geglu(x):
+    """x[..., :D] * gelu(x[..., D:]) for x [..., 2D] with a unit last stride (p2p_geglu)."""
+    _require_cuda(x)
+    D = x.shape[-1] // 2
+    x2 = x.reshape(-1, x.shape[-1])     # a view for the dense and row-strided inputs served here
+    if x.shape[-1] != 2 * D or x2.stride(-1) != 1 or x2.data_ptr() != x.data_ptr():
+        return None
+    g = GegluArgs()
+    out = x.new_empty(x.shape[:-1] + (D,))
+    g.inp, g.out = x2.data_ptr(), out.data_ptr()
+    g.in_row_stride, g.out_row_stride = x2.stride(0) if x2.shape[0] > 1 else 2 * D, D
+    g.rows, g.d = x2.shape[0], D
+    g.dtype = _glue_dtype(x)
+    return out if _glue_rc(lib().p2p_geglu(ctypes.byref(g), _stream(x.device)), "p2p_geglu") else None

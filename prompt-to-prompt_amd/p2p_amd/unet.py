@@ -14,11 +14,31 @@ down64 x2, down32 x2, down16 x2, mid8, up16 x3, up32 x3, up64 x3 (SURVEY §8 G1.
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import _hip
+
+# The norm / activation / bias / residual / GEGLU glue between the convolutions and GEMMs runs on
+# the HIP kernels of csrc/p2p_unet.hip (A/B switch, read once: 0 = the torch lines everywhere)
+FUSE_UNET = os.environ.get("P2P_FUSE_UNET", "1") != "0"
+
+
+def fused_glue(*tensors: torch.Tensor) -> bool:
+    """Whether a module takes its fused path: inference (grad mode off) on GPU tensors in bf16 or
+    f16, and the switch on.  Everything else -- CPU, f32, null-text inversion under autograd --
+    runs the torch lines."""
+    if not FUSE_UNET or torch.is_grad_enabled():
+        return False
+    return all(t.is_cuda and t.dtype in (torch.bfloat16, torch.float16) for t in tensors)
+
+
+def _norm_act(norm: nn.GroupNorm, x, **kw):
+    return _hip.group_norm(x, norm.weight, norm.bias, norm.num_groups, norm.eps, **kw)
 
 
 class CrossAttention(nn.Module):
@@ -58,7 +78,12 @@ class GEGLU(nn.Module):
         self.proj = nn.Linear(dim_in, dim_out * 2)
 
     def forward(self, x):
-        h, gate = self.proj(x).chunk(2, dim=-1)
+        p = self.proj(x)
+        if fused_glue(p):
+            out = _hip.geglu(p)
+            if out is not None:
+                return out
+        h, gate = p.chunk(2, dim=-1)
         return h * F.gelu(gate)
 
 
@@ -97,7 +122,27 @@ class Transformer2DModel(nn.Module):
         self.transformer_blocks = nn.ModuleList([BasicTransformerBlock(inner, n_heads, d_head, context_dim)])
         self.proj_out = nn.Conv2d(inner, in_channels, 1)
 
+    def _forward_fused(self, x, ctx):
+        """norm stores token-major, the 1x1 convs are GEMMs with a fused bias over the tokens, and
+        the residual kernel reads the tokens and writes NCHW."""
+        t = _norm_act(self.norm, x, tokens=True)
+        if t is None:
+            return None
+        b, c, h, w = x.shape
+        pi, po = self.proj_in, self.proj_out
+        t = F.linear(t, pi.weight.view(pi.out_channels, pi.in_channels), pi.bias)
+        for blk in self.transformer_blocks:
+            t = blk(t, context=ctx)
+        t = F.linear(t, po.weight.view(po.out_channels, po.in_channels), po.bias)
+        out = _hip.bias_residual(x, t, tokens=True)
+        # (the blocks have run, controllers included: finish here rather than run them again)
+        return out if out is not None else t.reshape(b, h, w, c).permute(0, 3, 1, 2) + x
+
     def forward(self, x, encoder_hidden_states=None):
+        if fused_glue(x, self.proj_in.weight):
+            out = self._forward_fused(x, encoder_hidden_states)
+            if out is not None:
+                return out
         b, c, h, w = x.shape
         res = x
         x = self.proj_in(self.norm(x))
@@ -118,7 +163,27 @@ class ResnetBlock2D(nn.Module):
         self.conv2 = nn.Conv2d(out_ch, out_ch, 3, padding=1)
         self.conv_shortcut = nn.Conv2d(in_ch, out_ch, 1) if in_ch != out_ch else None
 
+    def _forward_fused(self, x, temb):
+        """Both norms with their SiLU in one launch each; the convs run without bias: conv1's and
+        the time embedding are added on load by norm2, conv2's and the shortcut's by the residual."""
+        c1, c2, sc = self.conv1, self.conv2, self.conv_shortcut
+        h = _norm_act(self.norm1, x, silu=True)
+        if h is None:
+            return None
+        h = c1._conv_forward(h, c1.weight, None)
+        h = _norm_act(self.norm2, h, silu=True, chan_add=self.time_emb_proj(F.silu(temb)), chan_bias=c1.bias)
+        if h is None:
+            return None
+        h = c2._conv_forward(h, c2.weight, None)
+        if sc is not None:
+            return _hip.bias_residual(sc._conv_forward(x, sc.weight, None), h, c2.bias, sc.bias)
+        return _hip.bias_residual(x, h, c2.bias)
+
     def forward(self, x, temb):
+        if fused_glue(x, temb, self.conv1.weight):
+            out = self._forward_fused(x, temb)
+            if out is not None:
+                return out
         h = self.conv1(F.silu(self.norm1(x)))
         h = h + self.time_emb_proj(F.silu(temb))[:, :, None, None]
         h = self.conv2(F.silu(self.norm2(h)))
@@ -313,5 +378,6 @@ class UNet2DConditionModel(nn.Module):
             n = len(blk.resnets)
             res, skips = skips[-n:], skips[:-n]
             x = blk(x, emb, res, ctx)
-        x = self.conv_out(F.silu(self.conv_norm_out(x)))
+        h = _norm_act(self.conv_norm_out, x, silu=True) if fused_glue(x) else None
+        x = self.conv_out(h if h is not None else F.silu(self.conv_norm_out(x)))
         return {"sample": x}
