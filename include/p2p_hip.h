@@ -150,6 +150,17 @@ int p2p_cross_attn_fwd(const p2p_attn_tensors* t, const p2p_group* groups, int32
                        float* store, const int32_t* store_slot, int32_t store_accumulate,
                        p2p_stream_t stream);
 
+/* Which kernel the two calls above would launch: the same validation and the same selection
+ * (csrc/p2p_select.h), nothing launched and no pointer dereferenced beyond t and groups.  Returns
+ * the kernel's name as DESIGN.md §4 writes it ("self40_kernel<40,8,2,256>"; "…" stands for the
+ * precision's template arguments and D for head_dim), a static string, or NULL where the forward
+ * call would be rejected.  keeps_maps: some entry has store_slot >= 0 (p2p_self_attn_fwd with a
+ * store); wants_lse without keeps_maps: p2p_attn_fwd_lse; any_store: some entry of the cross call
+ * keeps its maps.  (Additive; ABI 16.) */
+const char* p2p_self_attn_kernel(const p2p_attn_tensors* t, int32_t keeps_maps, int32_t wants_lse);
+const char* p2p_cross_attn_kernel(const p2p_attn_tensors* t, const p2p_group* groups,
+                                  int32_t n_groups, int32_t any_store);
+
 /* Materialise mode, for controllers that override forward(attn, ...) (the reference
  * protocol, main.py:85-98): probs[n*H + h] = softmax(Q K^T * scale) as an f32
  * [n_batch * n_heads, n_query, n_key] tensor (ptp_utils.py:195-204).  key_mask (nullable,

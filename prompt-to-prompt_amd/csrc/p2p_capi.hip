@@ -102,11 +102,15 @@ const char* p2p_error_string(int code) {
   }
 }
 
-int p2p_self_attn_fwd(const p2p_attn_tensors* t, const int32_t* qk_src, float* store, const int32_t* store_slot,
-                      int32_t store_accumulate, float* lse_workspace, p2p_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// p2p_self_attn_fwd's arguments, validated, as the kernels' SelfArgs
+int fill_self(SelfArgs& a, const p2p_attn_tensors* t, const int32_t* qk_src, float* store, const int32_t* store_slot,
+              int32_t store_accumulate, float* lse_workspace) {
   int rc = check_tensors(t, true, true, true, true);
   if (rc) return rc;
-  SelfArgs a;
   fill_common(a, t);
   a.variant = self_variant();
   a.lse = nullptr;
@@ -125,19 +129,35 @@ int p2p_self_attn_fwd(const p2p_attn_tensors* t, const int32_t* qk_src, float* s
     a.store_accumulate = store_accumulate ? 1 : 0;
     a.lse = lse_workspace;
   }
-  // O (and, when maps are kept, every row's lse) in one fused pass; then the stored maps
-  rc = run_self(a, t->io_dtype, t->compute, t->head_dim, MODE_FUSED_, (hipStream_t)stream);
-  if (rc || a.n_maps == 0) return rc;
-  return run_self_maps(a, t->io_dtype, t->compute, t->head_dim, (hipStream_t)stream);
+  return 0;
 }
 
-int p2p_cross_attn_fwd(const p2p_attn_tensors* t, const p2p_group* groups, int32_t n_groups, float* store,
-                       const int32_t* store_slot, int32_t store_accumulate, p2p_stream_t stream) {
+// p2p_attn_fwd_lse's arguments, validated, as SelfArgs
+int fill_self_lse(SelfArgs& a, const p2p_attn_tensors* t, float* lse) {
+  int rc = check_tensors(t, true, true, true, true);
+  if (rc) return rc;
+  if (t->io_dtype == P2P_DTYPE_F16) return P2P_E_DTYPE;   // autograd pair: f32 / bf16 tensors only
+  if (!lse) return P2P_E_ARG;
+  if (t->compute != P2P_COMPUTE_BF16) return P2P_E_DTYPE;
+  fill_common(a, t);
+  a.variant = 0;
+  a.lse = lse;
+  a.probs = nullptr;
+  a.key_mask = nullptr;
+  for (int n = 0; n < t->n_batch; ++n) {
+    a.qk_src[n] = n;
+    a.store_slot[n] = -1;
+  }
+  return 0;
+}
+
+// p2p_cross_attn_fwd's arguments, validated, as the kernels' CrossArgs
+int fill_cross(CrossArgs& a, const p2p_attn_tensors* t, const p2p_group* groups, int32_t n_groups, float* store,
+               const int32_t* store_slot, int32_t store_accumulate) {
   int rc = check_tensors(t, true, true, true, true);
   if (rc) return rc;
   if (t->n_key > P2P_MAX_KEYS_CROSS) return P2P_E_KEYS;
   if (!groups || n_groups < 1 || n_groups > P2P_MAX_GROUPS) return P2P_E_BATCH;
-  CrossArgs a;
   a.variant = self_variant();
   fill_common(a, t);
   int covered = 0;
@@ -202,7 +222,62 @@ int p2p_cross_attn_fwd(const p2p_attn_tensors* t, const p2p_group* groups, int32
       if (groups[g].flags & P2P_PROGRAM_F_DENSE) a.edit_dense = 1;
       else a.edit_terms = 1;
     }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int p2p_self_attn_fwd(const p2p_attn_tensors* t, const int32_t* qk_src, float* store, const int32_t* store_slot,
+                      int32_t store_accumulate, float* lse_workspace, p2p_stream_t stream) {
+  SelfArgs a;
+  int rc = fill_self(a, t, qk_src, store, store_slot, store_accumulate, lse_workspace);
+  if (rc) return rc;
+  // O (and, when maps are kept, every row's lse) in one fused pass; then the stored maps
+  rc = run_self(a, t->io_dtype, t->compute, t->head_dim, MODE_FUSED_, (hipStream_t)stream);
+  if (rc || a.n_maps == 0) return rc;
+  return run_self_maps(a, t->io_dtype, t->compute, t->head_dim, (hipStream_t)stream);
+}
+
+const char* p2p_self_attn_kernel(const p2p_attn_tensors* t, int32_t keeps_maps, int32_t wants_lse) {
+  SelfArgs a;
+  // a placeholder for the store / lse pointers: their presence, not their value, selects
+  float* const some = t ? static_cast<float*>(t->o) : nullptr;
+  int rc;
+  if (keeps_maps) {   // p2p_self_attn_fwd, the first entry's maps kept
+    int32_t slots[P2P_MAX_BATCH];
+    for (int n = 0; n < P2P_MAX_BATCH; ++n) slots[n] = n == 0 ? 0 : -1;
+    rc = fill_self(a, t, nullptr, some, slots, 0, some);
+  } else if (wants_lse) {   // p2p_attn_fwd_lse
+    rc = fill_self_lse(a, t, some);
+  } else {   // p2p_self_attn_fwd, O only
+    rc = fill_self(a, t, nullptr, nullptr, nullptr, 0, nullptr);
+  }
+  if (rc) return nullptr;
+  const int sel = select_self(a, t->io_dtype, t->compute, t->head_dim, MODE_FUSED_);
+  return sel < 0 ? nullptr : name((SelfKernel)sel);
+}
+
+int p2p_cross_attn_fwd(const p2p_attn_tensors* t, const p2p_group* groups, int32_t n_groups, float* store,
+                       const int32_t* store_slot, int32_t store_accumulate, p2p_stream_t stream) {
+  CrossArgs a;
+  int rc = fill_cross(a, t, groups, n_groups, store, store_slot, store_accumulate);
+  if (rc) return rc;
   return run_cross(a, t->io_dtype, t->compute, t->head_dim, (hipStream_t)stream);
+}
+
+const char* p2p_cross_attn_kernel(const p2p_attn_tensors* t, const p2p_group* groups, int32_t n_groups,
+                                  int32_t any_store) {
+  CrossArgs a;
+  // any_store: every entry keeps its maps (what a group with folded LocalBlend sums needs); the
+  // selection reads only whether some entry does
+  int32_t slots[P2P_MAX_BATCH];
+  for (int n = 0; n < P2P_MAX_BATCH; ++n) slots[n] = any_store ? 0 : -1;
+  float* const some = t ? static_cast<float*>(t->o) : nullptr;
+  if (fill_cross(a, t, groups, n_groups, any_store ? some : nullptr, slots, 0)) return nullptr;
+  const int sel = select_cross(a, t->io_dtype, t->compute, t->head_dim);
+  return sel < 0 ? nullptr : name((CrossKernel)sel);
 }
 
 int p2p_attn_probs(const p2p_attn_tensors* t, const uint8_t* key_mask, float* probs, p2p_stream_t stream) {
@@ -247,21 +322,9 @@ int p2p_localblend(const p2p_blend_args* a, p2p_stream_t stream) {
 }
 
 int p2p_attn_fwd_lse(const p2p_attn_tensors* t, float* lse, p2p_stream_t stream) {
-  int rc = check_tensors(t, true, true, true, true);
-  if (rc) return rc;
-  if (t->io_dtype == P2P_DTYPE_F16) return P2P_E_DTYPE;   // autograd pair: f32 / bf16 tensors only
-  if (!lse) return P2P_E_ARG;
-  if (t->compute != P2P_COMPUTE_BF16) return P2P_E_DTYPE;
   SelfArgs a;
-  fill_common(a, t);
-  a.variant = 0;
-  a.lse = lse;
-  a.probs = nullptr;
-  a.key_mask = nullptr;
-  for (int n = 0; n < t->n_batch; ++n) {
-    a.qk_src[n] = n;
-    a.store_slot[n] = -1;
-  }
+  const int rc = fill_self_lse(a, t, lse);
+  if (rc) return rc;
   return run_self(a, t->io_dtype, t->compute, t->head_dim, MODE_FUSED_, (hipStream_t)stream);
 }
 

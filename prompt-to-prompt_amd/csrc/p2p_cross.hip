@@ -20,7 +20,7 @@
 //   store: running sum [slot + h][p][w] (+)= P_e' (the wave's LDS slab makes whole 128-byte rows)
 //          and LocalBlend's word sums of the row (word order, as blend_wordsum_kernel)
 //   O_e  = P_e' V_e
-// Numerics equal the per-entry kernel's edit path (cross_attn_kernel in p2p_attn.hip).
+// Numerics equal the per-entry kernel's edit path (cross_attn_kernel in p2p_cross_entry.hip).
 #include "p2p_device.h"
 #include "p2p_kernels.h"
 
@@ -637,11 +637,11 @@ __global__ __launch_bounds__(64 * W, (group_occupancy<D, W, EDIT, STORE>())) voi
 }
 
 template <int D, int W>
-hipError_t launch_group(const CrossArgs& a, hipStream_t st) {
+hipError_t launch_group(const CrossArgs& a, CrossKernel k, hipStream_t st) {
   CrossArgs b = a;
   b.n_qtiles = (a.P + 32 * W - 1) / (32 * W);
-  const bool edit = a.edit_dense != 0;
-  const bool store = a.any_store != 0;
+  const bool edit = k == CROSS_GROUP_EDIT || k == CROSS_GROUP_EDIT_STORE;
+  const bool store = k == CROSS_GROUP_STORE || k == CROSS_GROUP_EDIT_STORE;
   const size_t dyn = store ? (size_t)W * 32 * a.K * sizeof(float) : 0;
   dim3 grid(b.n_qtiles * a.H * a.n_groups), block(64 * W);
   if (edit && store) launch_kernel((cross_group_kernel<D, W, true, true>), grid, block, dyn, st, b);
@@ -653,34 +653,15 @@ hipError_t launch_group(const CrossArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// bf16 inputs and compute (the caller checks), no term-plane (non-dense) programs, a compiled
-// head dim; anything else -- or an experiments-build A/B selecting the per-entry kernel --
-// launches cross_attn_kernel instead
-// The workgroup walks the group's entries one after another, so it only pays where the grid
-// still fills the chip: >= 2 workgroups per CU (G1/G7: 2 groups x 8 heads x 32 query tiles).
-// Smaller grids (the 32x32 / 16x16 / 8x8 layers) keep the per-entry kernel's parallelism, and so
-// do d = 80 / 160 at any size: with eight groups per U-Net call (configs[3], 1024 workgroups at
-// G2/G6) the group kernel -- four entries with their map stores walked in sequence -- measured
-// 228.5 us per launch against the per-entry kernel's 131.4 (profiles/r04/group_vs_entry_r04aj/);
-// at d = 40 it stays ahead (146.9 vs 215.0 us).  (The d = 80 / 160 instantiations remain in the
-// experiments build, variants 122 / 123.)
-bool cross_group_eligible(const CrossArgs& a, int d) {
-  if (a.edit_terms || a.K > P2P_MAX_KEYS_CROSS) return false;
-  const int wgs = a.n_groups * a.H * ((a.P + 127) / 128);
-#ifdef P2P_EXPERIMENTS
-  if (a.variant == 123) return d == 40 || d == 80 || d == 160;   // clock stamps (tools/group_stamps.py)
-#endif
-  return d == 40 && wgs >= 512;
-}
-
-int run_cross_group(const CrossArgs& a, int d, hipStream_t st) {
+// bf16 inputs and compute, no term-plane (non-dense) programs: which launches come here is
+// p2p_select.h's.  (The d = 80 / 160 instantiations remain in the experiments build, variant 123.)
+int launch_cross_group(const CrossArgs& a, int d, CrossKernel k, hipStream_t st) {
+  if (!is_group(k)) return P2P_E_ARG;
   switch (d) {
+    case 40: return (int)launch_group<40, 4>(a, k, st);
 #ifdef P2P_EXPERIMENTS
-    case 40: return (int)launch_group<40, 4>(a, st);
-    case 80: return (int)launch_group<80, 4>(a, st);
-    case 160: return (int)launch_group<160, 4>(a, st);
-#else
-    case 40: return (int)launch_group<40, 4>(a, st);
+    case 80: return (int)launch_group<80, 4>(a, k, st);
+    case 160: return (int)launch_group<160, 4>(a, k, st);
 #endif
     default: return P2P_E_HEAD_DIM;
   }

@@ -18,6 +18,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "p2p_select.h"
+
 namespace p2p {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -428,6 +432,8 @@ __device__ __forceinline__ void rmw_add_store(float* g, const float* slab, int c
 
 template <int MAXF4>
 __device__ __forceinline__ void store_rows_rmw(float* g, const float* slab, int cnt, bool accumulate, int lane) {
+  // (rmw_load + rmw_add_store written out: calling the two halves changes the generated code of
+  // cross_group_kernel<40,4,*,STORE>)
   constexpr int IT = (MAXF4 + 63) / 64;   // float4s per lane
   const int n4 = cnt / 4;
   const __amdgpu_buffer_rsrc_t rs = make_rsrc(g, (int64_t)cnt * 4);
@@ -451,6 +457,16 @@ __device__ __forceinline__ void store_rows_rmw(float* g, const float* slab, int 
     if (i < n4) reinterpret_cast<f32x4_t*>(g)[i] = buf[j];
   }
 }
+
+// Where a kernel finds its row sums when V's first padding column is 1 (D % 32 != 0): O^T row D
+// is register r of d tile dt, held by lane half h of the query's lane pair.
+template <int D>
+struct OnesCol {
+  static constexpr int dt = D / 32;
+  static constexpr int rr = D % 32;
+  static constexpr int h = (rr >> 2) & 1;
+  static constexpr int r = (rr & 3) + 4 * (rr >> 3);
+};
 
 // ------------------------------------------------------------------ V^T operand fragments
 // A operand of the PV MFMA for k-step s (16 keys) of a 32-key sub-block starting at LDS row
@@ -569,5 +585,47 @@ struct VStrideBf16 {
   static constexpr int dw0 = DV / 2;
   static constexpr int value = ((dw0 % 64) == 16 || (dw0 % 64) == 48) ? DV : (dw0 < 48 ? 96 : (dw0 < 80 ? 160 : 224));
 };
+
+// 1.0 as an I/O element (the ones column of a V image)
+template <typename E>
+__device__ __forceinline__ E one_elem();
+template <>
+__device__ __forceinline__ float one_elem<float>() { return 1.0f; }
+template <>
+__device__ __forceinline__ uint16_t one_elem<uint16_t>() { return 0x3F80; }  // bf16 1.0
+template <>
+__device__ __forceinline__ f16_t one_elem<f16_t>() { return f16_t(0x3C00); }  // f16 1.0
+
+// ------------------------------------------------------------------ launcher helpers (host)
+// A Precision of p2p_select.h as the kernels' template triple, and a head dim as a constant: a
+// launcher writes `with_precision(prec, [&](auto pr) { return with_head_dim(d, [&](auto dd) {
+// ... typename decltype(pr)::IO ..., decltype(dd)::value ... }); })`.
+template <typename IO_, typename MQ_, typename MP_>
+struct PrecTypes {
+  using IO = IO_;
+  using MQ = MQ_;
+  using MP = MP_;
+};
+
+template <typename F>
+int with_precision(int prec, F&& f) {
+  switch (prec) {
+    case PREC_F32: return f(PrecTypes<float, QkF32, MmaF32>{});
+    case PREC_SPLIT: return f(PrecTypes<float, QkSplit, MmaBf16>{});
+    case PREC_F16: return f(PrecTypes<f16_t, QkF16, MmaF16>{});
+    case PREC_BF16: return f(PrecTypes<uint16_t, QkBf16<uint16_t>, MmaBf16>{});
+    default: return prec < 0 ? prec : P2P_E_DTYPE;
+  }
+}
+
+template <typename F>
+int with_head_dim(int d, F&& f) {
+  switch (d) {
+#define P2P_CASE(DD) case DD: return f(std::integral_constant<int, DD>{});
+    P2P_FOR_EACH_D(P2P_CASE)
+#undef P2P_CASE
+    default: return P2P_E_HEAD_DIM;
+  }
+}
 
 }  // namespace p2p

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/p2p_hip.h"
+#include "p2p_select.h"
 
 namespace p2p {
 
@@ -91,28 +92,38 @@ struct CrossArgs {
   int grp_blh[P2P_MAX_GROUPS];
 };
 
-enum { MODE_FUSED_ = 0, MODE_PV_ = 3 };
+// The kernel a launch runs (p2p_select.h) from its arguments: what run_self / run_cross launch and
+// what the p2p_*_attn_kernel queries name.  A SelfKernel / CrossKernel, or a negative P2P_E_* code.
+inline int select_self(const SelfArgs& a, int io_dtype, int compute, int d, int mode) {
+  return select_self(io_dtype, compute, d, a.P, a.K, mode, a.lse != nullptr, a.n_maps > 0, a.variant);
+}
+inline int select_cross(const CrossArgs& a, int io_dtype, int compute, int d) {
+  return select_cross(io_dtype, compute, d, a.n_groups, a.H, a.P, a.K, a.edit_terms != 0, a.edit_dense != 0,
+                      a.any_store != 0, a.variant);
+}
 
+// select, then launch (p2p_dispatch.hip)
 int run_self(const SelfArgs& a, int io_dtype, int compute, int d, int mode, hipStream_t st);
-// AttentionStore epilogue of the self layers whose maps are kept: p = exp2(c s - lse) for the
-// entries a.map_entry[0 .. n_maps) (a.lse filled by a preceding MODE_FUSED launch)
+int run_cross(const CrossArgs& a, int io_dtype, int compute, int d, hipStream_t st);
+
+// The kernel files' launchers: "launch this form with these arguments", no decisions.
+// self_attn_fused_kernel / self_pv_kernel (p2p_self.hip)
+int launch_self_fused(const SelfArgs& a, int prec, int d, SelfKernel k, hipStream_t st);
+// self_attn_multi_kernel (p2p_selfmulti.hip): d = 40, bf16 / f32 inputs
+int launch_self_multi(const SelfArgs& a, SelfKernel k, hipStream_t st);
+// self40_kernel (p2p_self40.hip): d = 40 / 80, bf16 / fp16 inputs, O only
+int launch_self40(const SelfArgs& a, SelfKernel k, hipStream_t st);
+// self_split_kernel / self_halves_kernel / self_ring_kernel (p2p_selfsplit.hip): d = 160, bf16, O only
+int launch_self_split(const SelfArgs& a, SelfKernel k, hipStream_t st);
+// AttentionStore epilogue of the self layers whose maps are kept (p2p_selfmaps.hip): p = exp2(c s -
+// lse) for the entries a.map_entry[0 .. n_maps) (a.lse filled by a preceding MODE_FUSED_ launch)
 int run_self_maps(const SelfArgs& a, int io_dtype, int compute, int d, hipStream_t st);
 // materialise protocol: probs (a.store) [N*H, P, K] = softmax(Q K^T * scale), optional key mask
 int run_self_probs(const SelfArgs& a, int io_dtype, int compute, int d, hipStream_t st);
-int run_cross(const CrossArgs& a, int io_dtype, int compute, int d, hipStream_t st);
-// group-coupled cross-attention (p2p_cross.hip): bf16 inputs and compute, dense or no programs
-bool cross_group_eligible(const CrossArgs& a, int d);
-int run_cross_group(const CrossArgs& a, int d, hipStream_t st);
-// d = 40 / 80 self-attention with bf16 (or, f16_inputs, fp16) inputs, O only (p2p_self40.hip): the
-// G1/G7 and G2/G6 production kernels
-bool self40_eligible(const SelfArgs& a, int d);
-int run_self40(const SelfArgs& a, int d, hipStream_t st, bool f16_inputs = false);
-// d = 160 self-attention with bf16 inputs, O only, K <= 256 (p2p_selfsplit.hip): key-split waves
-bool self_split_eligible(const SelfArgs& a, int d);
-int run_self_split(const SelfArgs& a, int d, hipStream_t st);
-// d = 160 self-attention with bf16 inputs, O only, K > 128: 4-stage global_load_lds ring
-bool self_ring_eligible(const SelfArgs& a, int d);
-int run_self_ring(const SelfArgs& a, int d, hipStream_t st);
+// cross_attn_kernel, one workgroup per entry (p2p_cross_entry.hip)
+int launch_cross_entry(const CrossArgs& a, int prec, int d, CrossKernel k, hipStream_t st);
+// cross_group_kernel, one workgroup per prompt group (p2p_cross.hip): bf16 inputs and compute
+int launch_cross_group(const CrossArgs& a, int d, CrossKernel k, hipStream_t st);
 int run_localblend(const p2p_blend_args& a, hipStream_t st);
 int run_latent_step(const p2p_latent_step_args& a, hipStream_t st);
 

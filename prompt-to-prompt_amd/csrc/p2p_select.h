@@ -1,0 +1,285 @@
+// Which kernel runs for a shape: the one place that decides.  Plain C++17, no HIP: the two pure
+// functions below map (dtype, compute, head dim, sizes, what the caller wants back) to a kernel
+// form, p2p_dispatch.hip launches that form, and p2p_self_attn_kernel / p2p_cross_attn_kernel
+// report it by name (tests/test_select.py pins the table on the CPU).  The kernel files export
+// launchers only; every threshold, with the measurement behind it, lives here.
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/p2p_hip.h"
+
+namespace p2p {
+
+enum { MODE_FUSED_ = 0, MODE_PV_ = 3 };
+
+// ---------------------------------------------------------------------------- precision, head dim
+// (io_dtype, compute) -> the (IO, MQ, MP) triple of the kernels: exact-f32 check mode; the bf16
+// pipe on f32 inputs (split-bf16 QK^T so the logits keep f32 grade, bf16 PV); bf16 inputs (one
+// bf16 MFMA per step, exact products); fp16 inputs (one f16 MFMA per step, exact products, f16 PV).
+enum Precision { PREC_F32 = 0, PREC_SPLIT, PREC_BF16, PREC_F16 };
+
+inline int select_precision(int io_dtype, int compute) {
+  if (compute == P2P_COMPUTE_F32) return io_dtype == P2P_DTYPE_F32 ? (int)PREC_F32 : (int)P2P_E_DTYPE;
+  if (io_dtype == P2P_DTYPE_F32) return PREC_SPLIT;
+  if (io_dtype == P2P_DTYPE_F16) return PREC_F16;
+  if (io_dtype == P2P_DTYPE_BF16) return PREC_BF16;
+  return P2P_E_DTYPE;
+}
+
+// the head dims with compiled kernels
+#define P2P_FOR_EACH_D(X) X(8) X(16) X(32) X(40) X(64) X(80) X(128) X(160)
+
+inline bool head_dim_compiled(int d) {
+  switch (d) {
+#define P2P_CASE(DD) case DD:
+    P2P_FOR_EACH_D(P2P_CASE)
+#undef P2P_CASE
+    return true;
+    default: return false;
+  }
+}
+
+// ---------------------------------------------------------------------------- self attention
+// family of a self kernel form: which file's launcher takes it
+enum SelfFamily { FAM_FUSED, FAM_PV, FAM_MULTI, FAM_SELF40, FAM_SPLIT, FAM_HALVES, FAM_RING };
+// row-statistics form of self_attn_fused_kernel
+enum SelfForm { FORM_DEFAULT, FORM_EXACT, FORM_NOMAX };
+
+// X(id, family, key tile | key blocks per wave, waves, form, name): "…" stands for the precision
+// triple and D for the head dim, both inputs of the selection -- so a name (and a test that asserts
+// it) tells the kernel family, tile shape and form, not which precision's or head dim's
+// instantiation the launcher then takes; that step is with_precision / with_head_dim
+// (p2p_device.h), one switch each, covered by the numeric tests.  The split 3x2 / 4x2 shapes and the
+// experiments forms are compiled but never selected by a production build.
+#define P2P_SELF_KERNELS(X)                                                                              \
+  X(SELF_FUSED_32x2, FAM_FUSED, 32, 2, FORM_DEFAULT, "self_attn_fused_kernel<…,D,32,2>")                 \
+  X(SELF_FUSED_32x2_EXACT, FAM_FUSED, 32, 2, FORM_EXACT, "self_attn_fused_kernel<…,D,32,2,EXACT>")       \
+  X(SELF_FUSED_32x4, FAM_FUSED, 32, 4, FORM_DEFAULT, "self_attn_fused_kernel<…,D,32,4>")                 \
+  X(SELF_FUSED_32x4_EXACT, FAM_FUSED, 32, 4, FORM_EXACT, "self_attn_fused_kernel<…,D,32,4,EXACT>")       \
+  X(SELF_FUSED_64x2, FAM_FUSED, 64, 2, FORM_DEFAULT, "self_attn_fused_kernel<…,D,64,2>")                 \
+  X(SELF_FUSED_64x2_EXACT, FAM_FUSED, 64, 2, FORM_EXACT, "self_attn_fused_kernel<…,D,64,2,EXACT>")       \
+  X(SELF_FUSED_64x2_NOMAX, FAM_FUSED, 64, 2, FORM_NOMAX, "self_attn_fused_kernel<…,D,64,2,NOMAX>")       \
+  X(SELF_FUSED_64x4, FAM_FUSED, 64, 4, FORM_DEFAULT, "self_attn_fused_kernel<…,D,64,4>")                 \
+  X(SELF_FUSED_64x4_EXACT, FAM_FUSED, 64, 4, FORM_EXACT, "self_attn_fused_kernel<…,D,64,4,EXACT>")       \
+  X(SELF_FUSED_64x4_NOMAX, FAM_FUSED, 64, 4, FORM_NOMAX, "self_attn_fused_kernel<…,D,64,4,NOMAX>")       \
+  X(SELF_FUSED_64x8, FAM_FUSED, 64, 8, FORM_DEFAULT, "self_attn_fused_kernel<…,D,64,8>")                 \
+  X(SELF_FUSED_64x8_EXACT, FAM_FUSED, 64, 8, FORM_EXACT, "self_attn_fused_kernel<…,D,64,8,EXACT>")       \
+  X(SELF_FUSED_64x8_NOMAX, FAM_FUSED, 64, 8, FORM_NOMAX, "self_attn_fused_kernel<…,D,64,8,NOMAX>")       \
+  X(SELF_PV_32x4, FAM_PV, 32, 4, FORM_DEFAULT, "self_pv_kernel<…,D,32,4>")                               \
+  X(SELF_PV_64x4, FAM_PV, 64, 4, FORM_DEFAULT, "self_pv_kernel<…,D,64,4>")                               \
+  X(SELF_MULTI_F16_256, FAM_MULTI, 256, 8, FORM_NOMAX, "self_attn_multi_kernel<…,40,256,8,2,F16,PIPE>")  \
+  X(SELF_MULTI_128, FAM_MULTI, 128, 8, FORM_NOMAX, "self_attn_multi_kernel<…,40,128,8,2>")               \
+  X(SELF40_D40, FAM_SELF40, 256, 8, FORM_NOMAX, "self40_kernel<40,8,2,256>")                             \
+  X(SELF40_D40_H16, FAM_SELF40, 256, 8, FORM_NOMAX, "self40_kernel<40,8,2,256,H16>")                     \
+  X(SELF40_D40_ROUND3, FAM_SELF40, 256, 8, FORM_NOMAX, "self40_kernel<40,8,2,256,FORM=17281>")           \
+  X(SELF40_D40_STAMPS, FAM_SELF40, 256, 8, FORM_NOMAX, "self40_kernel<40,8,2,256,STAMPS>")               \
+  X(SELF40_D80, FAM_SELF40, 128, 8, FORM_NOMAX, "self40_kernel<80,8,1,128>")                             \
+  X(SELF40_D80_H16, FAM_SELF40, 128, 8, FORM_NOMAX, "self40_kernel<80,8,1,128,H16>")                     \
+  X(SELF40_D80_STAMPS, FAM_SELF40, 128, 8, FORM_NOMAX, "self40_kernel<80,8,1,128,STAMPS>")               \
+  X(SELF_SPLIT_1x1, FAM_SPLIT, 1, 1, FORM_DEFAULT, "self_split_kernel<160,1,1>")                         \
+  X(SELF_SPLIT_2x1, FAM_SPLIT, 1, 2, FORM_DEFAULT, "self_split_kernel<160,2,1>")                         \
+  X(SELF_SPLIT_2x2, FAM_SPLIT, 2, 2, FORM_DEFAULT, "self_split_kernel<160,2,2>")                         \
+  X(SELF_SPLIT_3x2, FAM_SPLIT, 2, 3, FORM_DEFAULT, "self_split_kernel<160,3,2>")                         \
+  X(SELF_SPLIT_4x2, FAM_SPLIT, 2, 4, FORM_DEFAULT, "self_split_kernel<160,4,2>")                         \
+  X(SELF_HALVES, FAM_HALVES, 32, 4, FORM_DEFAULT, "self_halves_kernel")                                  \
+  X(SELF_RING, FAM_RING, 32, 4, FORM_DEFAULT, "self_ring_kernel<160,4>")
+
+enum SelfKernel {
+#define P2P_ENUM(id, fam, bk, w, form, nm) id,
+  P2P_SELF_KERNELS(P2P_ENUM)
+#undef P2P_ENUM
+  SELF_KERNEL_COUNT
+};
+
+struct SelfKernelInfo {
+  SelfFamily family;
+  int bk;      // keys per tile (split family: 32-key blocks per wave)
+  int waves;
+  SelfForm form;
+  const char* name;
+};
+
+inline const SelfKernelInfo& self_info(SelfKernel k) {
+  static const SelfKernelInfo table[SELF_KERNEL_COUNT] = {
+#define P2P_INFO(id, fam, bk, w, form, nm) {fam, bk, w, form, nm},
+      P2P_SELF_KERNELS(P2P_INFO)
+#undef P2P_INFO
+  };
+  return table[k];
+}
+inline const char* name(SelfKernel k) { return self_info(k).name; }
+
+// Key tile of self_attn_fused_kernel / self_pv_kernel: 32 keys at d >= 128 and for the f32 P V
+// (mp16 false: MP::kElemBytes == 4), else 64.  The launchers take their compile-time BK from here.
+constexpr int fused_bk(int d, bool mp16) { return (d >= 128 || !mp16) ? 32 : 64; }
+
+// self_attn_fused_kernel's form of a tile shape: EXACT and, where the table has it, NOMAX follow
+// the shape's DEFAULT row
+constexpr SelfKernel fused_form(SelfKernel shape, SelfForm form) { return (SelfKernel)(shape + (int)form); }
+static_assert(SELF_FUSED_32x2_EXACT == SELF_FUSED_32x2 + FORM_EXACT && SELF_FUSED_32x4_EXACT == SELF_FUSED_32x4 + FORM_EXACT &&
+                  SELF_FUSED_64x2_EXACT == SELF_FUSED_64x2 + FORM_EXACT && SELF_FUSED_64x4_EXACT == SELF_FUSED_64x4 + FORM_EXACT &&
+                  SELF_FUSED_64x8_EXACT == SELF_FUSED_64x8 + FORM_EXACT,
+              "EXACT follows DEFAULT");
+static_assert(SELF_FUSED_64x2_NOMAX == SELF_FUSED_64x2 + FORM_NOMAX && SELF_FUSED_64x4_NOMAX == SELF_FUSED_64x4 + FORM_NOMAX &&
+                  SELF_FUSED_64x8_NOMAX == SELF_FUSED_64x8 + FORM_NOMAX,
+              "NOMAX follows EXACT (64-key shapes only: the 32-key shapes have no NOMAX row)");
+
+// self_attn_fused_kernel's shape and form for a launch no specialised kernel takes
+inline SelfKernel select_fused(int prec, int d, int P, bool lse, bool maps) {
+  const bool mp16 = prec != PREC_F32;                 // 16-bit P V (MP::kElemBytes == 2)
+  const int bk = fused_bk(d, mp16);
+  // 8 waves x 32 query rows per workgroup, 64-key tiles (measured best at d = 40 and within 2 % of
+  // best at d = 80: tools/attn_bench.py, profiles/); else 2 waves up to 64 rows, 4 above
+  const int waves = (bk == 64 && (d == 40 || d == 80) && P > 64) ? 8 : P <= 64 ? 2 : 4;
+  SelfForm form = FORM_DEFAULT;
+  // kept maps: the lse feeds the stored maps, exact f32 row sums
+  if (maps) form = FORM_EXACT;
+  // O only (no lse) with a ones column (d % 32 != 0) and bf16 P: no per-tile max (p grows with
+  // the f32 exponent range; f16 P keeps the defer-max loop, p <= 2^8)
+  else if (!lse && bk == 64 && d % 32 != 0 && (prec == PREC_BF16 || prec == PREC_SPLIT)) form = FORM_NOMAX;
+  const SelfKernel base = bk == 32 ? (waves == 2 ? SELF_FUSED_32x2 : SELF_FUSED_32x4)
+                                   : (waves == 2 ? SELF_FUSED_64x2 : waves == 4 ? SELF_FUSED_64x4 : SELF_FUSED_64x8);
+  return fused_form(base, form);   // (NOMAX only with bk == 64, above)
+}
+
+// The kernel a self launch runs, or a negative P2P_E_* code.  mode: MODE_FUSED_ (O, and the lse when
+// `lse` or `maps`) or MODE_PV_ (the materialise protocol's P V).  variant: P2P_SELF_VARIANT of the
+// experiments build (A/B timing tools), 0 in production.
+inline int select_self(int io_dtype, int compute, int d, int P, int K, int mode, bool lse, bool maps,
+                       int variant) {
+  const int prec = select_precision(io_dtype, compute);
+  if (prec < 0) return prec;
+  if (!head_dim_compiled(d)) return P2P_E_HEAD_DIM;
+  (void)variant;
+  if (mode == MODE_PV_) return fused_bk(d, prec != PREC_F32) == 32 ? SELF_PV_32x4 : SELF_PV_64x4;
+  lse = lse || maps;
+  const bool o_only = !lse;   // nothing but O wanted: no kept maps, no autograd
+  // d = 40 / 80 with bf16 or fp16 inputs, O only (G1/G7, G2/G6): the software-pipelined kernel of
+  // p2p_self40.hip, from the sizes where its 512- / 256-query workgroups and 256- / 128-key tiles
+  // fill (d = 40: P >= 2048; d = 80: P >= 512; both K >= 256)
+  if (o_only && (prec == PREC_BF16 || prec == PREC_F16) && K >= 256) {
+    const bool h16 = prec == PREC_F16;   // fp16: the launch shapes of the bf16 defaults (K's
+                                         // packed-u16 range check has nothing to check)
+    if (d == 40 && P >= 2048) {
+      if (h16) return SELF40_D40_H16;
+#ifdef P2P_EXPERIMENTS
+      if (variant == 163) return SELF40_D40_STAMPS;   // default with clock stamps
+      if (variant == 17281) return SELF40_D40_ROUND3; // round-3 default
+#endif
+      // LEAN fragments, split staging (waves 0-3 K, 4-7 V), the younger half holding priority 1 on
+      // three of every four steps (round 3: 0.1867 ms vs 0.1880-0.1885 for priority on alternate
+      // step pairs and 0.2056 for round 2, profiles/r03/g1_ab/r03y_ab.log), and K's f16 range check
+      // as a packed-u16 maximum (round 4: 0.1864-0.1865 vs 0.1881-0.1889 ms,
+      // profiles/r04/ab/g1_r04h.log)
+      return SELF40_D40;
+    }
+    if (d == 80 && P >= 512) {
+      if (h16) return SELF40_D80_H16;
+#ifdef P2P_EXPERIMENTS
+      if (variant == 164) return SELF40_D80_STAMPS;   // default + stamps
+#endif
+      // d = 80: 8 waves x ONE 32-row query block (two waves per SIMD), 128-key tiles, split staging
+      // and the younger half's priority duty of the d = 40 kernel.  In the pipeline (bench.py,
+      // HIP events) 36.8-37.2 -> 30.9-31.2 us against round 4's 4 waves x 2 blocks (one wave per
+      // SIMD), which is as fast only with hot inputs: the second wave hides the cold Q / K / V
+      // loads the layer meets after its QKV GEMM (profiles/r05/d80_ab/; 4 x 1 x 64: 34.0, 8 x 1 x
+      // 64: 35.9, without split staging or priority: 32.0-33.0)
+      return SELF40_D80;
+    }
+  }
+  // d = 40, O only, P >= 2048, what self40_kernel leaves: the multi-block kernel (bf16 / f32
+  // inputs only; fp16 takes the per-tile kernel below).  bf16 inputs with K < 256: its F16 form
+  // on 256-key tiles; f32 inputs (split-bf16 Q K^T, two K planes): 128-key tiles
+  if (o_only && d == 40 && P >= 2048) {
+    if (prec == PREC_BF16) return SELF_MULTI_F16_256;
+    if (prec == PREC_SPLIT) return SELF_MULTI_128;
+  }
+  // d = 160, bf16 inputs, O only (the 16x16 / 8x8 layers): p2p_selfsplit.hip
+  if (o_only && d == 160 && prec == PREC_BF16 && K >= 1) {
+    // K <= 128 (the 8x8 layers): the waves of a 32-query workgroup split the keys (W = ceil(K / 64)
+    // waves of 64 keys, or 2 x 32 for K <= 64).  Measured against the per-tile kernel
+    // (tools/small_bench.py, profiles/r03/small): 8x8 (K = 64) 7.84 -> 6.21 us; 16x16 (K = 256)
+    // 14.73 -> 16.51 us -- every 32-query workgroup then pulls the head's whole K and V through its
+    // CU (4x the per-tile kernel's L2 -> CU traffic), so K > 128 keeps per-tile kernels:
+    if (K <= 32) return SELF_SPLIT_1x1;
+    if (K <= 64) return SELF_SPLIT_2x1;
+    if (K <= 128) return SELF_SPLIT_2x2;
+    // K <= 256 (16x16): two halves of the keys per 64-query workgroup; above, the 4-stage
+    // global_load_lds ring
+    return K <= 256 ? SELF_HALVES : SELF_RING;
+  }
+  return select_fused(prec, d, P, lse, maps);
+}
+
+// ---------------------------------------------------------------------------- cross attention
+// X(id, name): the group kernel's EDIT / STORE forms, and the per-entry kernel with its waves and
+// whether the dense mapper tile is staged
+#define P2P_CROSS_KERNELS(X)                                            \
+  X(CROSS_GROUP, "cross_group_kernel<D,4>")                             \
+  X(CROSS_GROUP_STORE, "cross_group_kernel<D,4,STORE>")                 \
+  X(CROSS_GROUP_EDIT, "cross_group_kernel<D,4,EDIT>")                   \
+  X(CROSS_GROUP_EDIT_STORE, "cross_group_kernel<D,4,EDIT,STORE>")       \
+  X(CROSS_ENTRY_W2, "cross_attn_kernel<…,D,2>")                         \
+  X(CROSS_ENTRY_W4, "cross_attn_kernel<…,D,4>")                         \
+  X(CROSS_ENTRY_W4_DENSE, "cross_attn_kernel<…,D,4,DENSE>")
+
+enum CrossKernel {
+#define P2P_ENUM(id, nm) id,
+  P2P_CROSS_KERNELS(P2P_ENUM)
+#undef P2P_ENUM
+  CROSS_KERNEL_COUNT
+};
+
+inline const char* name(CrossKernel k) {
+  static const char* const table[CROSS_KERNEL_COUNT] = {
+#define P2P_NAME(id, nm) nm,
+      P2P_CROSS_KERNELS(P2P_NAME)
+#undef P2P_NAME
+  };
+  return table[k];
+}
+inline bool is_group(CrossKernel k) { return k <= CROSS_GROUP_EDIT_STORE; }
+static_assert(CROSS_GROUP_STORE == CROSS_GROUP + 1 && CROSS_GROUP_EDIT == CROSS_GROUP + 2 &&
+                  CROSS_GROUP_EDIT_STORE == CROSS_GROUP + 3,
+              "select_cross adds 2 for EDIT and 1 for STORE");
+
+// Waves of cross_attn_kernel: 4, 2 for the f32 P V (mp16 false) at d >= 128.  The launcher takes
+// its compile-time W from here.
+constexpr int cross_waves(int d, bool mp16) { return (!mp16 && d >= 128) ? 2 : 4; }
+
+// The kernel a cross launch runs, or a negative P2P_E_* code.  edit_terms / edit_dense: some group
+// edits through the term planes / carries the dense f16 mapper tile; any_store: some entry keeps
+// its maps.
+inline int select_cross(int io_dtype, int compute, int d, int n_groups, int H, int P, int K, bool edit_terms,
+                        bool edit_dense, bool any_store, int variant) {
+  const int prec = select_precision(io_dtype, compute);
+  if (prec < 0) return prec;
+  if (K > P2P_MAX_KEYS_CROSS) return P2P_E_KEYS;
+  if (!head_dim_compiled(d)) return P2P_E_HEAD_DIM;
+  (void)variant;
+  // The group-coupled kernel (p2p_cross.hip): bf16 inputs and compute, no term-plane (non-dense)
+  // programs (fp16 takes the per-entry kernel).
+  // The workgroup walks the group's entries one after another, so it only pays where the grid
+  // still fills the chip: >= 2 workgroups per CU (G1/G7: 2 groups x 8 heads x 32 query tiles).
+  // Smaller grids (the 32x32 / 16x16 / 8x8 layers) keep the per-entry kernel's parallelism, and so
+  // do d = 80 / 160 at any size: with eight groups per U-Net call (configs[3], 1024 workgroups at
+  // G2/G6) the group kernel -- four entries with their map stores walked in sequence -- measured
+  // 228.5 us per launch against the per-entry kernel's 131.4 (profiles/r04/group_vs_entry_r04aj/);
+  // at d = 40 it stays ahead (146.9 vs 215.0 us).  (The d = 80 / 160 instantiations remain in the
+  // experiments build, variant 123.)
+  if (prec == PREC_BF16 && !edit_terms) {
+    const int wgs = n_groups * H * ((P + 127) / 128);
+    bool group = d == 40 && wgs >= 512;
+#ifdef P2P_EXPERIMENTS
+    if (variant == 123) group = d == 40 || d == 80 || d == 160;   // clock stamps (tools/group_stamps.py)
+#endif
+    if (group) return CROSS_GROUP + (edit_dense ? 2 : 0) + (any_store ? 1 : 0);
+  }
+  if (prec == PREC_F32) return cross_waves(d, false) == 2 ? CROSS_ENTRY_W2 : CROSS_ENTRY_W4;
+  // the dense path (16-bit P V only) forms the edit as one MFMA product with the mapper tile;
+  // a launch that mixes dense and term-plane programs gathers all of them
+  return (edit_dense && !edit_terms) ? CROSS_ENTRY_W4_DENSE : CROSS_ENTRY_W4;
+}
+
+}  // namespace p2p

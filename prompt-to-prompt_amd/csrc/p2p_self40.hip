@@ -709,48 +709,25 @@ hipError_t launch(const SelfArgs& a, hipStream_t st) {
 
 }  // namespace
 
-bool self40_eligible(const SelfArgs& a, int d) {
-  if (d == 40) return a.P >= 2048 && a.K >= 256;
-  if (d == 80) return a.P >= 512 && a.K >= 256;
-  return false;
-}
-
-// variant: 0 = production shapes; the experiments build also honours the A/B shapes below
-// (every other measured shape is in git history; DESIGN.md §4 and profiles/ hold the logs)
-int run_self40(const SelfArgs& a, int d, hipStream_t st, bool f16_inputs) {
+// every decision is p2p_select.h's: the forms below are the instantiations it names (FORM bits as
+// documented above the kernel; every other measured shape is in git history, DESIGN.md §4 and
+// profiles/ hold the logs)
+int launch_self40(const SelfArgs& a, SelfKernel k, hipStream_t st) {
 #ifdef S40_ONLY
   return (int)launch<S40_ONLY>(a, st);
 #else
-  // fp16 inputs: the launch shapes of the bf16 defaults below (K's packed-u16 range check has
-  // nothing to check)
-  if (f16_inputs) {
-    if (d == 80) return (int)launch<80, 8, 1, 128, true, 1 | 128 | 256 | 512 | 16384, true>(a, st);
-    return (int)launch<40, 8, 2, 256, true, 1 | 128 | 256 | 512 | 16384, true>(a, st);
-  }
-  if (d == 80) {
-    switch (a.variant) {
+  constexpr int kBase = 1 | 128 | 256 | 512 | 16384;
+  switch (k) {
+    case SELF40_D40: return (int)launch<40, 8, 2, 256, true, kBase | 8388608>(a, st);
+    case SELF40_D40_H16: return (int)launch<40, 8, 2, 256, true, kBase, true>(a, st);
+    case SELF40_D40_ROUND3: return (int)launch<40, 8, 2, 256, true, kBase>(a, st);
+    case SELF40_D80: return (int)launch<80, 8, 1, 128, true, kBase>(a, st);
+    case SELF40_D80_H16: return (int)launch<80, 8, 1, 128, true, kBase, true>(a, st);
 #ifdef P2P_EXPERIMENTS
-      case 164: return (int)launch<80, 8, 1, 128, true, 1 | 128 | 256 | 512 | 16384 | 16>(a, st);  // default + stamps
+    case SELF40_D40_STAMPS: return (int)launch<40, 8, 2, 256, true, 17281 | 8388608 | 16>(a, st);
+    case SELF40_D80_STAMPS: return (int)launch<80, 8, 1, 128, true, kBase | 16>(a, st);
 #endif
-      // d = 80: 8 waves x ONE 32-row query block (two waves per SIMD), 128-key tiles, split staging
-      // and the younger half's priority duty of the d = 40 kernel.  In the pipeline (bench.py,
-      // HIP events) 36.8-37.2 -> 30.9-31.2 us against round 4's 4 waves x 2 blocks (one wave per
-      // SIMD), which is as fast only with hot inputs: the second wave hides the cold Q / K / V
-      // loads the layer meets after its QKV GEMM (profiles/r05/d80_ab/; 4 x 1 x 64: 34.0, 8 x 1 x
-      // 64: 35.9, without split staging or priority: 32.0-33.0)
-      default: return (int)launch<80, 8, 1, 128, true, 1 | 128 | 256 | 512 | 16384>(a, st);
-    }
-  }
-  switch (a.variant) {
-#ifdef P2P_EXPERIMENTS
-    case 163: return (int)launch<40, 8, 2, 256, true, 17281 | 8388608 | 16>(a, st);   // default with clock stamps
-#endif
-    case 17281: return (int)launch<40, 8, 2, 256, true, 1 | 128 | 256 | 512 | 16384>(a, st);   // round-3 default
-    // LEAN fragments, split staging (waves 0-3 K, 4-7 V), the younger half holding priority 1 on
-    // three of every four steps (round 3: 0.1867 ms vs 0.1880-0.1885 for priority on alternate step
-    // pairs and 0.2056 for round 2, profiles/r03/g1_ab/r03y_ab.log), and K's f16 range check as a
-    // packed-u16 maximum (round 4: 0.1864-0.1865 vs 0.1881-0.1889 ms, profiles/r04/ab/g1_r04h.log)
-    default: return (int)launch<40, 8, 2, 256, true, 1 | 128 | 256 | 512 | 16384 | 8388608>(a, st);
+    default: return P2P_E_ARG;
   }
 #endif
 }

@@ -518,39 +518,26 @@ hipError_t launch_ring(const SelfArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// d = 160, bf16 inputs, O only, K > 128: the 4-stage DMA ring
-bool self_ring_eligible(const SelfArgs& a, int d) {
-  return d == 160 && a.K > 128 && a.lse == nullptr && a.n_maps == 0;
-}
-
-int run_self_ring(const SelfArgs& a, int d, hipStream_t st) {
-  (void)d;
-  if (a.K <= 256) {
-    SelfArgs b = a;
-    b.n_qtiles = (a.P + 63) / 64;
-    dim3 grid(b.n_qtiles * a.H * a.N), block(256);
-    launch_kernel(self_halves_kernel, grid, block, 0, st, b);
-    return (int)hipGetLastError();
+// d = 160, bf16 inputs, O only: which K takes which form is p2p_select.h's (a split form covers
+// W x KBW x 32 keys; 3 x 2 and 4 x 2 are compiled but not selected: splitting K > 128 measured
+// slower than the per-tile kernels)
+int launch_self_split(const SelfArgs& a, SelfKernel k, hipStream_t st) {
+  switch (k) {
+    case SELF_SPLIT_1x1: return (int)launch_split<160, 1, 1>(a, st);
+    case SELF_SPLIT_2x1: return (int)launch_split<160, 2, 1>(a, st);
+    case SELF_SPLIT_2x2: return (int)launch_split<160, 2, 2>(a, st);
+    case SELF_SPLIT_3x2: return (int)launch_split<160, 3, 2>(a, st);
+    case SELF_SPLIT_4x2: return (int)launch_split<160, 4, 2>(a, st);
+    case SELF_HALVES: {
+      SelfArgs b = a;
+      b.n_qtiles = (a.P + 63) / 64;
+      dim3 grid(b.n_qtiles * a.H * a.N), block(256);
+      launch_kernel(self_halves_kernel, grid, block, 0, st, b);
+      return (int)hipGetLastError();
+    }
+    case SELF_RING: return (int)launch_ring<4>(a, st);
+    default: return P2P_E_ARG;
   }
-  return (int)launch_ring<4>(a, st);
-}
-
-// d = 160, bf16 inputs, O only, K <= 128 (the 8x8 layers): the waves split the keys (W =
-// ceil(K / 64) waves of 64 keys, or 2 x 32 for K <= 64).  Measured against the per-tile kernel
-// (tools/small_bench.py, profiles/r03/small): 8x8 (K = 64) 7.84 -> 6.21 us; 16x16 (K = 256)
-// 14.73 -> 16.51 us -- every 32-query workgroup then pulls the head's whole K and V through its
-// CU (4x the per-tile kernel's L2 -> CU traffic), so K > 128 keeps the per-tile kernel
-bool self_split_eligible(const SelfArgs& a, int d) {
-  return d == 160 && a.K >= 1 && a.K <= 128 && a.lse == nullptr && a.n_maps == 0;
-}
-
-int run_self_split(const SelfArgs& a, int d, hipStream_t st) {
-  (void)d;
-  if (a.K <= 32) return (int)launch_split<160, 1, 1>(a, st);
-  if (a.K <= 64) return (int)launch_split<160, 2, 1>(a, st);
-  if (a.K <= 128) return (int)launch_split<160, 2, 2>(a, st);
-  if (a.K <= 192) return (int)launch_split<160, 3, 2>(a, st);
-  return (int)launch_split<160, 4, 2>(a, st);
 }
 
 }  // namespace p2p

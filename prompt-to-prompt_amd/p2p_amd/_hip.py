@@ -127,10 +127,15 @@ def lib():
             raise HipError(f"{_LIB_PATH} is missing: run __graft_entry__.build() (make -C prompt-to-prompt_amd/csrc)")
         L = ctypes.CDLL(_LIB_PATH)
         i32, vp, f32, i64 = ctypes.c_int32, ctypes.c_void_p, ctypes.c_float, ctypes.c_int64
-        L.p2p_abi_version.restype = ctypes.c_int
-        L.p2p_error_string.restype = ctypes.c_char_p
-        L.p2p_source_hash.restype = ctypes.c_char_p
+        # every export returns int, but for these
+        other = {"p2p_error_string": ctypes.c_char_p, "p2p_source_hash": ctypes.c_char_p,
+                 "p2p_self_attn_kernel": ctypes.c_char_p, "p2p_cross_attn_kernel": ctypes.c_char_p,
+                 "p2p_attn_bwd_workspace": ctypes.c_int64}
+        for fn in EXPORTED_SYMBOLS:
+            getattr(L, fn).restype = other.get(fn, ctypes.c_int)
         L.p2p_error_string.argtypes = [ctypes.c_int]
+        L.p2p_self_attn_kernel.argtypes = [ctypes.POINTER(AttnTensors), i32, i32]
+        L.p2p_cross_attn_kernel.argtypes = [ctypes.POINTER(AttnTensors), vp, i32, i32]
         L.p2p_self_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, i32, vp, vp]
         L.p2p_cross_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp, i32, vp, vp, i32, vp]
         L.p2p_attn_probs.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp]
@@ -141,16 +146,11 @@ def lib():
         L.p2p_attn_fwd_lse.argtypes = [ctypes.POINTER(AttnTensors), vp, vp]
         L.p2p_attn_bwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
         L.p2p_attn_bwd_workspace.argtypes = [ctypes.POINTER(AttnTensors)]
-        L.p2p_attn_bwd_workspace.restype = ctypes.c_int64
         L.p2p_group_norm.argtypes = [ctypes.POINTER(GroupNormArgs), vp]
         L.p2p_bias_residual.argtypes = [ctypes.POINTER(BiasResidualArgs), vp]
         L.p2p_geglu.argtypes = [ctypes.POINTER(GegluArgs), vp]
         L.p2p_clock_probe.argtypes = [vp, i32, i32, vp]
         L.p2p_set_launch_events.argtypes = [vp, vp]
-        for fn in ("p2p_self_attn_fwd", "p2p_cross_attn_fwd", "p2p_attn_probs", "p2p_attn_pv",
-                   "p2p_localblend", "p2p_store_scale", "p2p_latent_step", "p2p_attn_fwd_lse", "p2p_attn_bwd",
-                   "p2p_clock_probe", "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu"):
-            getattr(L, fn).restype = ctypes.c_int
         if L.p2p_abi_version() != ABI_VERSION:
             raise HipError(f"libp2p_hip.so ABI {L.p2p_abi_version()} != {ABI_VERSION}")
         _lib = L
@@ -175,7 +175,8 @@ def check_source_hash() -> str:
 EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p2p_self_attn_fwd", "p2p_cross_attn_fwd",
                     "p2p_attn_probs", "p2p_attn_pv", "p2p_localblend", "p2p_store_scale", "p2p_latent_step",
                     "p2p_attn_fwd_lse", "p2p_attn_bwd", "p2p_attn_bwd_workspace", "p2p_clock_probe",
-                    "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu")
+                    "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu",
+                    "p2p_self_attn_kernel", "p2p_cross_attn_kernel")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -284,20 +285,50 @@ def self_attn(q, k, v, o, heads, scale, compute="bf16", qk_src=None, store=None,
     _check(rc, "p2p_self_attn_fwd")
 
 
+def self_attn_kernel(t: AttnTensors, keeps_maps: bool = False, wants_lse: bool = False) -> Optional[str]:
+    """The kernel p2p_self_attn_fwd (or, wants_lse, p2p_attn_fwd_lse) launches for these tensors, as
+    the library names it (csrc/p2p_select.h), or None where it rejects them.  Launches nothing."""
+    name = lib().p2p_self_attn_kernel(ctypes.byref(t), int(bool(keeps_maps)), int(bool(wants_lse)))
+    return name.decode() if name is not None else None
+
+
+def cross_attn_kernel(t: AttnTensors, G, any_store: bool = False) -> Optional[str]:
+    """The same for p2p_cross_attn_fwd with the Group array G."""
+    name = lib().p2p_cross_attn_kernel(ctypes.byref(t), G, len(G), int(bool(any_store)))
+    return name.decode() if name is not None else None
+
+
+def _group_array(t: AttnTensors, groups):
+    """The p2p_group array of cross_attn's group tuples."""
+    G = (Group * len(groups))()
+    for i, grp in enumerate(groups):
+        first, count, prog, alpha = grp[:4]
+        blend = grp[4] if len(grp) > 4 else None
+        hints = int(grp[5]) if len(grp) > 5 else 0
+        G[i].first, G[i].count = int(first), int(count)
+        G[i].program = prog.data_ptr() if prog is not None else None
+        G[i].alpha = alpha.data_ptr() if alpha is not None else None
+        G[i].flags = (int(getattr(prog, "p2p_flags", 0)) | hints) if prog is not None else (hints & GROUP_F_SHARED_KV)
+        G[i].n_edits = int(getattr(prog, "p2p_n_edits", 0)) if prog is not None else 0
+        if blend is not None:
+            sums, balpha, bsub, col, lh = blend
+            _require_cuda(sums, balpha, bsub)
+            assert sums.dtype == torch.float32 and sums.is_contiguous() and sums.numel() == count * 2 * lh * t.n_query
+            assert balpha.dtype == torch.float32 and balpha.is_contiguous() and balpha.shape == (count, t.n_key)
+            assert bsub is None or (bsub.dtype == torch.float32 and bsub.is_contiguous() and bsub.shape == balpha.shape)
+            G[i].blend_sums, G[i].blend_alpha = sums.data_ptr(), balpha.data_ptr()
+            G[i].blend_sub = bsub.data_ptr() if bsub is not None else None
+            G[i].blend_col, G[i].blend_lh = int(col), int(lh)
+    return G
+
+
 def cross_group_dispatch(t: AttnTensors, groups) -> bool:
-    """Whether p2p_cross_attn_fwd runs cross_group_kernel for these arguments: the rule of
-    run_cross / cross_group_eligible (p2p_attn.hip, p2p_cross.hip) -- bf16 inputs and compute, no
-    term-plane program, K <= 96, d = 40, and >= 512 workgroups (groups x heads x 128-row query
-    tiles).  Labels only (bench.py); the library decides."""
-    if t.io_dtype != P2P_DTYPE_BF16 or t.compute != P2P_COMPUTE_BF16 or t.n_key > MAX_KEYS_CROSS:
-        return False
-    if t.head_dim != 40:
-        return False
-    for grp in groups:
-        prog, count = grp[2], int(grp[1])
-        if prog is not None and count > 1 and not (int(getattr(prog, "p2p_flags", 0)) & 1):
-            return False
-    return len(groups) * t.n_heads * ((t.n_query + 127) // 128) >= 512
+    """Whether p2p_cross_attn_fwd runs cross_group_kernel for these arguments (cross_attn's group
+    tuples): the library's own answer (p2p_cross_attn_kernel; the rule is csrc/p2p_select.h's)."""
+    G = _group_array(t, groups)
+    # folded LocalBlend sums need every entry to store; the group / per-entry choice ignores stores
+    any_store = any(len(grp) > 4 and grp[4] is not None for grp in groups)
+    return (cross_attn_kernel(t, G, any_store) or "").startswith("cross_group_kernel")
 
 
 SHARED_KV_HINTS = os.environ.get("P2P_SHARED_KV", "1") != "0"   # (A/B switch: 0 = never hint)
@@ -319,25 +350,7 @@ def cross_attn(q, k, v, o, heads, scale, groups, compute="bf16", store=None, sto
     None, col, lh): LocalBlend's word sums folded into the store epilogue (p2p_group.blend_*); hints:
     per-call p2p_group.flags bits OR'ed onto the program's (GROUP_F_R_ONLY)."""
     t = make_tensors(q, k, v, o, heads, scale, compute)
-    G = (Group * len(groups))()
-    for i, grp in enumerate(groups):
-        first, count, prog, alpha = grp[:4]
-        blend = grp[4] if len(grp) > 4 else None
-        hints = int(grp[5]) if len(grp) > 5 else 0
-        G[i].first, G[i].count = int(first), int(count)
-        G[i].program = prog.data_ptr() if prog is not None else None
-        G[i].alpha = alpha.data_ptr() if alpha is not None else None
-        G[i].flags = (int(getattr(prog, "p2p_flags", 0)) | hints) if prog is not None else (hints & GROUP_F_SHARED_KV)
-        G[i].n_edits = int(getattr(prog, "p2p_n_edits", 0)) if prog is not None else 0
-        if blend is not None:
-            sums, balpha, bsub, col, lh = blend
-            _require_cuda(sums, balpha, bsub)
-            assert sums.dtype == torch.float32 and sums.is_contiguous() and sums.numel() == count * 2 * lh * t.n_query
-            assert balpha.dtype == torch.float32 and balpha.is_contiguous() and balpha.shape == (count, t.n_key)
-            assert bsub is None or (bsub.dtype == torch.float32 and bsub.is_contiguous() and bsub.shape == balpha.shape)
-            G[i].blend_sums, G[i].blend_alpha = sums.data_ptr(), balpha.data_ptr()
-            G[i].blend_sub = bsub.data_ptr() if bsub is not None else None
-            G[i].blend_col, G[i].blend_lh = int(col), int(lh)
+    G = _group_array(t, groups)
     slots = _i32_array(store_slot) if store_slot is not None else None
     if store is not None:
         _require_cuda(store)

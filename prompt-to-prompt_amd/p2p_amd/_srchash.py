@@ -1,17 +1,24 @@
-"""Content hash of the HIP sources that libp2p_hip.so is built from.
+"""The list of HIP sources that libp2p_hip.so is built from, and their content hash.
 
-The Makefile stamps this value into the library (``p2p_source_hash()``); ``_hip.check_source_hash``
-recomputes it from the tree at run time, so a stale prebuilt binary (the .so is git-ignored and
-travels to the GPU box as a file) cannot pass ``smoke()`` or the GPU tests.
+This is the one list: the Makefile takes its ``SRCS`` and ``HDRS`` from here (``--sources`` /
+``--headers``) and stamps the hash into the library (``p2p_source_hash()``);
+``_hip.check_source_hash`` recomputes it from the tree at run time, so a stale prebuilt binary (the
+.so is git-ignored and travels to the GPU box as a file) cannot pass ``smoke()`` or the GPU tests.
 Run as a script it prints the hash (the Makefile's ``$(shell ...)``).
 """
 import hashlib
 import os
+import sys
 
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
+# one translation unit each, slowest first (make starts them in this order)
+SOURCES = ("p2p_generic.hip", "p2p_self40.hip", "p2p_selfmaps.hip", "p2p_selfmulti.hip", "p2p_selfsplit.hip",
+           "p2p_cross.hip", "p2p_bwd.hip", "p2p_blend.hip", "p2p_unet.hip", "p2p_dispatch.hip", "p2p_capi.hip")
+# what the sources include: the headers, and the two files p2p_generic.hip compiles as one object
+HEADERS = ("p2p_device.h", "p2p_kernels.h", "p2p_select.h", "../../include/p2p_hip.h", "p2p_self.hip",
+           "p2p_cross_entry.hip")
 # every file whose text reaches the compiler or the link line, in a fixed order
-FILES = ("p2p_attn.hip", "p2p_self40.hip", "p2p_selfsplit.hip", "p2p_cross.hip", "p2p_bwd.hip", "p2p_blend.hip", "p2p_unet.hip", "p2p_capi.hip", "p2p_device.h", "p2p_kernels.h",
-         "../../include/p2p_hip.h", "Makefile")
+FILES = SOURCES + HEADERS + ("Makefile",)
 
 
 def source_hash() -> str:
@@ -25,4 +32,9 @@ def source_hash() -> str:
 
 
 if __name__ == "__main__":
-    print(source_hash())
+    if "--sources" in sys.argv:
+        print(" ".join(SOURCES))
+    elif "--headers" in sys.argv:
+        print(" ".join(HEADERS))
+    else:
+        print(source_hash())

@@ -13,6 +13,7 @@ from test_gpu_kernels import make_qkv, ref_out, ref_probs
 
 pytestmark = pytest.mark.gpu
 
+TUNED_KERNEL = {40: "self40_kernel<40,8,2,256,H16>", 80: "self40_kernel<80,8,1,128,H16>"}
 SELECT_TUNED = [  # (N, P, K, H, d, j)
     (2, 2048, 2048, 2, 40, 5), (2, 2048, 2048, 2, 40, 2000), (2, 2100, 2100, 2, 40, 2090),
     (2, 1024, 1024, 2, 80, 5), (2, 1100, 1100, 2, 80, 1090),
@@ -21,12 +22,17 @@ SELECT_TUNED = [  # (N, P, K, H, d, j)
 
 @pytest.mark.parametrize("geom", SELECT_TUNED, ids=lambda g: "x".join(map(str, g)))
 def test_selection_self_bit_exact_tuned_shapes(cuda, geom):
+    N, P, K, H, d, _ = geom
+    q, kv = torch.empty(N, P, H * d, dtype=F16, device=cuda), torch.empty(N, K, H * d, dtype=F16, device=cuda)
+    assert _hip.self_attn_kernel(_hip.make_tensors(q, kv, kv, q, H, d ** -0.5, "bf16")) == TUNED_KERNEL[d]
     check_selection_self(geom)
 
 
 # ------------------------------------------------------------------ 2. accuracy at the tuned shapes
 def _check_self(q, k, v, H, d, src=None):
     o = torch.empty_like(q)
+    # the launch below takes the tuned kernel's fp16 form (the library's own answer)
+    assert _hip.self_attn_kernel(_hip.make_tensors(q, k, v, o, H, d ** -0.5, "bf16")) == TUNED_KERNEL[d]
     _hip.self_attn(q, k, v, o, H, d ** -0.5, compute="bf16", qk_src=src)
     want = ref_out(ref_probs(q, k, H, d ** -0.5, qk_src=src), v, H)
     assert torch.isfinite(o.float()).all()

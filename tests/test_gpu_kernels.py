@@ -147,6 +147,8 @@ def test_self_attention_f16_form(cuda, case):
         k[0, 150, :d] = 10.0
     src = [0, 0] if case == "remap" else None
     o = torch.empty_like(q)
+    assert _hip.self_attn_kernel(_hip.make_tensors(q, k, v, o, H, d ** -0.5, "bf16")) == (
+        "self_attn_multi_kernel<…,40,256,8,2,F16,PIPE>" if case == "multi_late_peak" else "self40_kernel<40,8,2,256>")
     _hip.self_attn(q, k, v, o, H, d ** -0.5, compute="bf16", qk_src=src)
     want = ref_out(ref_probs(q, k, H, d ** -0.5, qk_src=src), v, H)
     assert torch.isfinite(o.float()).all()
@@ -168,6 +170,7 @@ def test_self_attention_d80_pipelined(cuda, case):
         k[0, 700, :d] = 60.0            # key 700 (tile 5 of 128): c s ~ 3.3e4 log2 units
     src = [0, 0] if case == "remap" else None
     o = torch.empty_like(q)
+    assert _hip.self_attn_kernel(_hip.make_tensors(q, k, v, o, H, d ** -0.5, "bf16")) == "self40_kernel<80,8,1,128>"
     _hip.self_attn(q, k, v, o, H, d ** -0.5, compute="bf16", qk_src=src)
     want = ref_out(ref_probs(q, k, H, d ** -0.5, qk_src=src), v, H)
     assert torch.isfinite(o.float()).all()
@@ -319,8 +322,8 @@ def _edit_mapper(B, K, weight=0.5):
 
 
 # (P, d, K, heads, prompt groups, kernel the launch must dispatch to): run_cross takes
-# cross_group_kernel only when n_groups x heads x ceil(P / 128) >= 512 (p2p_cross.hip
-# cross_group_eligible), so the group-kernel cases are sized to clear that bar
+# cross_group_kernel only when n_groups x heads x ceil(P / 128) >= 512 (p2p_select.h
+# select_cross), so the group-kernel cases are sized to clear that bar
 CROSS_GROUP_CASES = [
     (4096, 40, 77, 8, 1, "group"), (4096, 40, 77, 8, 2, "group"),     # G1/G7
     (4000, 40, 96, 8, 2, "group"),                                    # ragged P, K = 96: no short key tail
@@ -412,6 +415,10 @@ def test_self_attention_key_split_d160(cuda, case):
     q, k, v = make_qkv(N, P, K, H, d, torch.bfloat16, qscale=32.0 if case == "peaky32" else 1.0, seed=41)
     src = [0, 1, 0, 0] if case == "remap" else None
     o = torch.empty_like(q)
+    want_kernel = ("self_split_kernel<160,1,1>" if K <= 32 else "self_split_kernel<160,2,1>" if K <= 64 else
+                   "self_split_kernel<160,2,2>" if K <= 128 else "self_halves_kernel" if K <= 256 else
+                   "self_ring_kernel<160,4>")
+    assert _hip.self_attn_kernel(_hip.make_tensors(q, k, v, o, H, d ** -0.5, "bf16")) == want_kernel
     _hip.self_attn(q, k, v, o, H, d ** -0.5, compute="bf16", qk_src=src)
     want = ref_out(ref_probs(q, k, H, d ** -0.5, qk_src=src), v, H)
     assert torch.isfinite(o.float()).all()

@@ -14,7 +14,7 @@ COLS = programs.PROGRAM_COLS
 
 
 def run_blob(blob: np.ndarray, P0: np.ndarray, Pb: np.ndarray, alpha: np.ndarray) -> np.ndarray:
-    """Reference interpreter of the kernel's edit step (p2p_attn.hip cross_attn_kernel): every
+    """Reference interpreter of the kernel's edit step (p2p_cross_entry.hip cross_attn_kernel): every
     column walks the first tmax term planes."""
     hdr = blob[:32].view(np.int32)
     E, n, tmax = int(hdr[0]), int(hdr[1]), int(hdr[2])
