@@ -263,6 +263,51 @@ typedef struct {
 
 int p2p_latent_step(const p2p_latent_step_args* a, p2p_stream_t stream);
 
+/* The same latent update for the PLMS sampler (PNDM with skip_prk_steps: the scheduler of the
+ * Stable Diffusion v1.4 pipeline main.py:29 loads; p2p_amd/pndm.py), additive to ABI 16:
+ *   e     = eps_u + guidance * (eps_c - eps_u)        (cfg = 1, rounded in eps_dtype as above;
+ *                                                      else e = eps), upcast to f32
+ *   hist_out = e                                      (nullable: the scheduler's eps history)
+ *   m     = w[0] * e + w[1] * hist[0] + ... + w[n_hist] * hist[n_hist - 1]
+ *                                                     (f32 products summed left to right: the
+ *                                                      linear multistep combination, e.g.
+ *                                                      (55, -59, 37, -9) / 24 from the fourth call)
+ *   out   = sample_coeff * x - (eps_num * m) / eps_den          (one IEEE division)
+ * with, for the step from alpha_cumprod a_t to a_p, sample_coeff = sqrt(a_p / a_t), eps_num =
+ * a_p - a_t and eps_den = a_t * sqrt(1 - a_p) + sqrt(a_t * (1 - a_t) * a_p): the three host-side
+ * 0-dim values of PNDMScheduler.plan_step.  Then the LocalBlend blend of p2p_latent_step, in
+ * either form: mask / group_size / group_blend / blend_* mean what they mean there, with the same
+ * preconditions (in the blend_sums form also: every hist pointer in use and hist_out 16-byte
+ * aligned).  hist[i]: f32 [B, C, H, W], newest first; x is the sample the scheduler steps from (its
+ * kept sample on the corrector call).  Every f32 operation is rounded to nearest, none contracted,
+ * so out and hist_out are bit-identical to PNDMScheduler.step on the same inputs.
+ * Rejected with P2P_E_ARG before any launch: a NULL eps / x / out, n_hist outside 0..4, a NULL
+ * hist[i] below n_hist, hist_out equal to a hist[i] in use or to x or out, eps_den == 0. */
+typedef struct {
+  const void* eps;
+  int32_t eps_dtype;               /* P2P_DTYPE_*                                      */
+  int32_t cfg;
+  float guidance;
+  const float* x;
+  float* out;                      /* may alias x (not in the blend_sums form)         */
+  int32_t n_prompts, channels, height, width;
+  const uint8_t* mask;
+  int32_t group_size;
+  const uint8_t* group_blend;
+  const float* blend_sums[P2P_MAX_GROUPS];
+  int32_t blend_lh;
+  int32_t blend_res;
+  float blend_th_pool, blend_th_sub;
+  int32_t blend_sub;
+  const float* hist[4];            /* stored eps, newest first                         */
+  int32_t n_hist;                  /* 0..4 entries of hist used                        */
+  float w[5];                      /* w[0]: the new eps; w[1 + i]: hist[i]             */
+  float* hist_out;                 /* NULL, or f32 [B, C, H, W]: the new eps           */
+  float sample_coeff, eps_num, eps_den;
+} p2p_plms_step_args;
+
+int p2p_plms_step(const p2p_plms_step_args* a, p2p_stream_t stream);
+
 /* AttentionStore.get_average_attention (main.py:144-149): dst = src / divisor, computed as
  * src * (1.0f / divisor) -- what torch does for `cuda_tensor / python_scalar` on the
  * reference's cuda:0 device. */

@@ -315,20 +315,31 @@ struct DdimC {
   __device__ explicit DdimC(const p2p_latent_step_args& a)
       : cfg(a.cfg), guidance(a.guidance), sqrt_beta_t(a.sqrt_beta_t), sqrt_alpha_t(a.sqrt_alpha_t),
         sqrt_alpha_prev(a.sqrt_alpha_prev), sqrt_one_minus_alpha_prev(a.sqrt_one_minus_alpha_prev) {}
+  // the step-form interface of latent_blend_kernel: DDIM reads no tensor beside eps and x
+  struct Extra {};
+  __device__ __forceinline__ void load(Extra&, int64_t) const {}
+  __device__ __forceinline__ void store(int64_t, const f32x4_t&) const {}
+  template <int DT>
+  __device__ __forceinline__ float from(float eu, float ec, float x, const Extra&, int, float&) const;
 };
+
+// the CFG combine (ptp_utils.py:73) rounded in the eps dtype as torch rounds it
+template <int DT, typename A>
+__device__ __forceinline__ float cfg_noise(const A& a, float eu, float ec) {
+  auto rd = [](float v) { return DT == P2P_DTYPE_BF16 ? rnd_bf16(v) : DT == P2P_DTYPE_F16 ? rnd_f16(v) : v; };
+  if (a.cfg) {
+    const float diff = rd(sub_rn(ec, eu));
+    const float gd = rd(mul_rn(a.guidance, diff));
+    return rd(add_rn(eu, gd));
+  }
+  return eu;
+}
 
 // DT: the eps element type (P2P_DTYPE_*), i.e. the format torch's eager ops round to
 template <int DT, typename A>
 __device__ __forceinline__ float ddim_from(const A& a, float eu, float ec, float x) {
   auto rd = [](float v) { return DT == P2P_DTYPE_BF16 ? rnd_bf16(v) : DT == P2P_DTYPE_F16 ? rnd_f16(v) : v; };
-  float noise;
-  if (a.cfg) {
-    const float diff = rd(sub_rn(ec, eu));
-    const float gd = rd(mul_rn(a.guidance, diff));
-    noise = rd(add_rn(eu, gd));
-  } else {
-    noise = eu;
-  }
+  const float noise = cfg_noise<DT>(a, eu, ec);
   // a 0-dim f32 factor times a bf16 (f16) tensor: torch casts the factor to bf16 (f16) first
   const float t1 = rd(mul_rn(rd(a.sqrt_beta_t), noise));
   const float x0 = __fdiv_rn(sub_rn(x, t1), a.sqrt_alpha_t);
@@ -337,7 +348,56 @@ __device__ __forceinline__ float ddim_from(const A& a, float eu, float ec, float
 }
 
 template <int DT>
-__device__ __forceinline__ float eps_at(const p2p_latent_step_args& a, int64_t idx) {
+__device__ __forceinline__ float DdimC::from(float eu, float ec, float x, const Extra&, int, float&) const {
+  return ddim_from<DT>(*this, eu, ec, x);
+}
+
+// The PLMS step (PNDMScheduler.step, p2p_amd/pndm.py; include/p2p_hip.h p2p_plms_step): the
+// CFG-combined eps upcast to f32 (e_new, what the scheduler's history keeps), the linear multistep
+// combination m = w[0] e + w[1] h[0] + ... summed left to right, and the transfer
+// sample_coeff x - (eps_num m) / eps_den -- f32, every operation rounded on its own
+template <typename P>
+__device__ __forceinline__ float plms_transfer(const P& p, float e, const float* h, float x) {
+  float m = mul_rn(p.w[0], e);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < p.n_hist) m = add_rn(m, mul_rn(p.w[1 + k], h[k]));
+  return sub_rn(mul_rn(p.sample_coeff, x), __fdiv_rn(mul_rn(p.eps_num, m), p.eps_den));
+}
+
+// the PLMS step's scalars and history pointers by value (see DdimC).  The launcher points the
+// hist[] entries past n_hist at x, so all four loads of an element are valid and unconditional
+struct PlmsC {
+  int cfg, n_hist;
+  float guidance, w[5], sample_coeff, eps_num, eps_den;
+  const float* hist[4];
+  float* hist_out;
+  __device__ explicit PlmsC(const p2p_plms_step_args& a)
+      : cfg(a.cfg), n_hist(a.n_hist), guidance(a.guidance), w{a.w[0], a.w[1], a.w[2], a.w[3], a.w[4]},
+        sample_coeff(a.sample_coeff), eps_num(a.eps_num), eps_den(a.eps_den),
+        hist{a.hist[0], a.hist[1], a.hist[2], a.hist[3]}, hist_out(a.hist_out) {}
+  struct Extra { f32x4_t h[4]; };
+  __device__ __forceinline__ void load(Extra& e, int64_t idx) const {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e.h[k] = *reinterpret_cast<const f32x4_t*>(hist[k] + idx);
+  }
+  __device__ __forceinline__ void store(int64_t idx, const f32x4_t& e_new) const {
+    if (hist_out) *reinterpret_cast<f32x4_t*>(hist_out + idx) = e_new;
+  }
+  template <int DT>
+  __device__ __forceinline__ float from(float eu, float ec, float x, const Extra& e, int j, float& e_new) const {
+    e_new = cfg_noise<DT>(*this, eu, ec);
+    const float h[4] = {e.h[0][j], e.h[1][j], e.h[2][j], e.h[3][j]};
+    return plms_transfer(*this, e_new, h, x);
+  }
+};
+
+template <typename A> struct StepOf;
+template <> struct StepOf<p2p_latent_step_args> { using C = DdimC; };
+template <> struct StepOf<p2p_plms_step_args> { using C = PlmsC; };
+
+template <int DT, typename A>
+__device__ __forceinline__ float eps_at(const A& a, int64_t idx) {
   if constexpr (DT == P2P_DTYPE_BF16) return bf2f(static_cast<const uint16_t*>(a.eps)[idx]);
   else if constexpr (DT == P2P_DTYPE_F16) return h2f(static_cast<const uint16_t*>(a.eps)[idx]);
   else return static_cast<const float*>(a.eps)[idx];
@@ -345,14 +405,33 @@ __device__ __forceinline__ float eps_at(const p2p_latent_step_args& a, int64_t i
 
 // prev_sample of prompt b at element i of its [C, H, W] latent
 template <int DT>
-__device__ __forceinline__ float ddim_prev(const p2p_latent_step_args& a, int b, int64_t i, int64_t chw) {
+__device__ __forceinline__ float step_prev(const p2p_latent_step_args& a, int b, int64_t i, int64_t chw) {
   const float eu = eps_at<DT>(a, (int64_t)b * chw + i);
   const float ec = a.cfg ? eps_at<DT>(a, (int64_t)(a.n_prompts + b) * chw + i) : 0.f;
   return ddim_from<DT>(a, eu, ec, a.x[(int64_t)b * chw + i]);
 }
 
+// the same for the PLMS step, which also keeps the new eps (hist_out)
 template <int DT>
-__global__ __launch_bounds__(256) void latent_step_kernel(p2p_latent_step_args a, int64_t chw) {
+__device__ __forceinline__ float step_prev(const p2p_plms_step_args& a, int b, int64_t i, int64_t chw) {
+  const int64_t idx = (int64_t)b * chw + i;
+  const float eu = eps_at<DT>(a, idx);
+  const float ec = a.cfg ? eps_at<DT>(a, (int64_t)(a.n_prompts + b) * chw + i) : 0.f;
+  const float e = cfg_noise<DT>(a, eu, ec);
+  float h[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < a.n_hist) h[k] = a.hist[k][idx];
+  if (a.hist_out) a.hist_out[idx] = e;
+  return plms_transfer(a, e, h, a.x[idx]);
+}
+
+// A: p2p_latent_step_args (DDIM) or p2p_plms_step_args -- the step form is step_prev's overload.
+// (This body and latent_blend_kernel's stay in the kernels: moved into an inlined device function,
+// hipcc no longer folds the block size with the launch bounds and schedules the DDIM instantiations
+// differently; templated on the argument struct their ISA is the one-form kernels'.)
+template <int DT, typename A>
+__global__ __launch_bounds__(256) void latent_step_kernel(A a, int64_t chw) {
   const int HW = a.height * a.width;
   const int B = a.n_prompts;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -363,7 +442,7 @@ __global__ __launch_bounds__(256) void latent_step_kernel(p2p_latent_step_args a
     bool blend = false;
     for (int b = 0; b < B; ++b) {
       const int bg = b % gs;                              // position inside its group
-      float prev = ddim_prev<DT>(a, b, i, chw);
+      float prev = step_prev<DT>(a, b, i, chw);
       if (bg == 0) {
         prev0 = prev;                                     // the group's source prompt
         blend = a.mask && (!a.group_blend || a.group_blend[b / gs]);
@@ -384,9 +463,10 @@ __global__ __launch_bounds__(256) void latent_step_kernel(p2p_latent_step_args a
 // workgroup reads another's output.  The kernel is latency-bound (1 MB per step): every thread
 // issues its eps / x loads (4 pixels x 1 channel, for b and the source) before the mask build's,
 // so the launch waits about two memory round trips; 64 workgroups keep the per-thread DDIM
-// arithmetic (two IEEE divisions per element) short.
-template <int DT>
-__global__ __launch_bounds__(256, 1) void latent_blend_kernel(p2p_latent_step_args a, int64_t chw, int px_per_wg) {
+// arithmetic (two IEEE divisions per element) short.  The PLMS form (A = p2p_plms_step_args) adds
+// its four history loads per prompt to the same batch of loads and one store of the new eps.
+template <int DT, typename A>
+__global__ __launch_bounds__(256, 1) void latent_blend_kernel(A a, int64_t chw, int px_per_wg) {
   // every field this kernel reads, copied to scalars first (see DdimC)
   const int HW = a.height * a.width;
   const int b = blockIdx.y;
@@ -399,7 +479,8 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(p2p_latent_step_ar
   float* const og = a.out;
   const int lh = a.blend_lh, res = a.blend_res, use_sub = a.blend_sub;
   const float th_pool = a.blend_th_pool, th_sub = a.blend_th_sub;
-  const DdimC dc(a);
+  using StepC = typename StepOf<A>::C;
+  const StepC dc(a);
   const bool blend = bg != 0 && ws != nullptr;          // workgroup-uniform
   __shared__ BlendLds L;
   // a workgroup covers px_per_wg = 256 pixels x 4 channels per pass: thread t takes channel
@@ -428,12 +509,14 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(p2p_latent_step_ar
     const int64_t i = (int64_t)min(c, C - 1) * HW + pxc;
     Raw reu[2], rec[2];
     f32x4_t xv[2];
+    typename StepC::Extra ex[2];
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       const int bb = s2 ? b0 : b;
       reu[s2] = ld_eps((int64_t)bb * chw + i);
       rec[s2] = ld_eps((int64_t)((dc.cfg ? NP : 0) + bb) * chw + i);
       xv[s2] = *reinterpret_cast<const f32x4_t*>(xg + (int64_t)bb * chw + i);
+      dc.load(ex[s2], (int64_t)bb * chw + i);
     }
     if (blend && c0 == 0) {
       const int R2 = res * res;
@@ -442,31 +525,36 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(p2p_latent_step_ar
     if (c >= C || px >= HW) continue;
     const f32x4_t eu = unpack(reu[0]), ec = unpack(rec[0]);
     f32x4_t o;
+    float e_new[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float prev = ddim_from<DT>(dc, eu[j], ec[j], xv[0][j]);
+      float prev = dc.template from<DT>(eu[j], ec[j], xv[0][j], ex[0], j, e_new[j]);
       if (blend) {
         const f32x4_t eu0 = unpack(reu[1]), ec0 = unpack(rec[1]);
-        const float prev0 = ddim_from<DT>(dc, eu0[j], ec0[j], xv[1][j]);
+        float e0;
+        const float prev0 = dc.template from<DT>(eu0[j], ec0[j], xv[1][j], ex[1], j, e0);
         const float m = L.msrc[blend_src_of(px + j, res, H, W)];
         prev = add_rn(prev0, mul_rn(m, sub_rn(prev, prev0)));
       }
       o[j] = prev;
     }
     *reinterpret_cast<f32x4_t*>(og + (int64_t)b * chw + (int64_t)c * HW + px) = o;
+    dc.store((int64_t)b * chw + (int64_t)c * HW + px, f32x4_t{e_new[0], e_new[1], e_new[2], e_new[3]});
   }
 }
 
-int run_latent_step(const p2p_latent_step_args& a, hipStream_t st) {
+// The checks and launch geometry the DDIM and PLMS latent steps share.  Returns a P2P_E_* code, or
+// 0 with `fused` telling which form launches (the one-launch LocalBlend, or the plain / mask form)
+template <typename A>
+static int check_latent_args(const A& a, bool& fused) {
   if (!a.eps || !a.x || !a.out || a.n_prompts < 1 || a.channels < 1 || a.height < 1 || a.width < 1 ||
       a.group_size < 0 || (a.group_size > 0 && a.n_prompts % a.group_size))
     return P2P_E_ARG;
   if (a.eps_dtype != P2P_DTYPE_F32 && a.eps_dtype != P2P_DTYPE_BF16 && a.eps_dtype != P2P_DTYPE_F16)
     return P2P_E_DTYPE;
-  const int64_t chw = (int64_t)a.channels * a.height * a.width;
   const int gs = a.group_size > 0 ? a.group_size : a.n_prompts;
   const int n_groups = a.n_prompts / gs;
-  bool fused = false;
+  fused = false;
   for (int g = 0; g < P2P_MAX_GROUPS; ++g) {
     if (!a.blend_sums[g]) continue;
     if (g >= n_groups) return P2P_E_ARG;
@@ -479,25 +567,73 @@ int run_latent_step(const p2p_latent_step_args& a, hipStream_t st) {
         ((uintptr_t)a.x | (uintptr_t)a.out | (uintptr_t)a.eps) % 16 ||
         a.blend_res * a.blend_res > 256 || a.blend_res > a.height || a.blend_res > a.width)
       return P2P_E_ARG;
-    constexpr int kPx = 256;    // latent pixels per workgroup (x 4 channels: 256 threads x 4 elements)
+  }
+  return 0;
+}
+
+constexpr int kLatentPx = 256;    // latent pixels per workgroup (x 4 channels: 256 threads x 4 elements)
+
+int run_latent_step(const p2p_latent_step_args& a, hipStream_t st) {
+  bool fused = false;
+  if (const int rc = check_latent_args(a, fused)) return rc;
+  const int64_t chw = (int64_t)a.channels * a.height * a.width;
+  if (fused) {
     const int hw = a.height * a.width;
-    dim3 grid((hw + kPx - 1) / kPx, a.n_prompts);
+    dim3 grid((hw + kLatentPx - 1) / kLatentPx, a.n_prompts);
     if (a.eps_dtype == P2P_DTYPE_BF16)
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_BF16>, grid, dim3(256), 0, st, a, chw, kPx);
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_BF16, p2p_latent_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
     else if (a.eps_dtype == P2P_DTYPE_F16)
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_F16>, grid, dim3(256), 0, st, a, chw, kPx);
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_F16, p2p_latent_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
     else
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_F32>, grid, dim3(256), 0, st, a, chw, kPx);
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_F32, p2p_latent_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
     return (int)hipGetLastError();
   }
   int64_t blocks = (chw + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (a.eps_dtype == P2P_DTYPE_BF16)
-    launch_kernel(latent_step_kernel<P2P_DTYPE_BF16>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+    launch_kernel(latent_step_kernel<P2P_DTYPE_BF16, p2p_latent_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
   else if (a.eps_dtype == P2P_DTYPE_F16)
-    launch_kernel(latent_step_kernel<P2P_DTYPE_F16>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+    launch_kernel(latent_step_kernel<P2P_DTYPE_F16, p2p_latent_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
   else
-    launch_kernel(latent_step_kernel<P2P_DTYPE_F32>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+    launch_kernel(latent_step_kernel<P2P_DTYPE_F32, p2p_latent_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+  return (int)hipGetLastError();
+}
+
+int run_plms_step(const p2p_plms_step_args& in, hipStream_t st) {
+  bool fused = false;
+  if (const int rc = check_latent_args(in, fused)) return rc;
+  if (in.n_hist < 0 || in.n_hist > 4 || in.eps_den == 0.f) return P2P_E_ARG;
+  if (in.hist_out && (in.hist_out == in.x || in.hist_out == in.out)) return P2P_E_ARG;
+  uintptr_t ptr_bits = (uintptr_t)in.hist_out;
+  for (int k = 0; k < in.n_hist; ++k) {
+    if (!in.hist[k] || in.hist[k] == in.hist_out) return P2P_E_ARG;
+    ptr_bits |= (uintptr_t)in.hist[k];
+  }
+  if (fused && ptr_bits % 16) return P2P_E_ARG;
+  p2p_plms_step_args a = in;
+  // the one-launch form loads all four history slots of an element unconditionally: the unused
+  // ones read x (a valid f32 tensor of the same shape, 16-byte aligned), and are discarded
+  for (int k = a.n_hist; k < 4; ++k) a.hist[k] = a.x;
+  const int64_t chw = (int64_t)a.channels * a.height * a.width;
+  if (fused) {
+    const int hw = a.height * a.width;
+    dim3 grid((hw + kLatentPx - 1) / kLatentPx, a.n_prompts);
+    if (a.eps_dtype == P2P_DTYPE_BF16)
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_BF16, p2p_plms_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
+    else if (a.eps_dtype == P2P_DTYPE_F16)
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_F16, p2p_plms_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
+    else
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_F32, p2p_plms_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
+    return (int)hipGetLastError();
+  }
+  int64_t blocks = (chw + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (a.eps_dtype == P2P_DTYPE_BF16)
+    launch_kernel(latent_step_kernel<P2P_DTYPE_BF16, p2p_plms_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+  else if (a.eps_dtype == P2P_DTYPE_F16)
+    launch_kernel(latent_step_kernel<P2P_DTYPE_F16, p2p_plms_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+  else
+    launch_kernel(latent_step_kernel<P2P_DTYPE_F32, p2p_plms_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
   return (int)hipGetLastError();
 }
 

@@ -90,6 +90,21 @@ class LatentArgs(ctypes.Structure):
     ]
 
 
+class PlmsArgs(ctypes.Structure):
+    _fields_ = [
+        ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("cfg", ctypes.c_int32),
+        ("guidance", ctypes.c_float), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("n_prompts", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("mask", ctypes.c_void_p), ("group_size", ctypes.c_int32), ("group_blend", ctypes.c_void_p),
+        ("blend_sums", ctypes.c_void_p * MAX_GROUPS), ("blend_lh", ctypes.c_int32), ("blend_res", ctypes.c_int32),
+        ("blend_th_pool", ctypes.c_float), ("blend_th_sub", ctypes.c_float), ("blend_sub", ctypes.c_int32),
+        ("hist", ctypes.c_void_p * 4), ("n_hist", ctypes.c_int32), ("w", ctypes.c_float * 5),
+        ("hist_out", ctypes.c_void_p),
+        ("sample_coeff", ctypes.c_float), ("eps_num", ctypes.c_float), ("eps_den", ctypes.c_float),
+    ]
+
+
 class GroupNormArgs(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("chan_add", ctypes.c_void_p), ("chan_add_stride", ctypes.c_int64),
@@ -143,6 +158,7 @@ def lib():
         L.p2p_localblend.argtypes = [ctypes.POINTER(BlendArgs), vp]
         L.p2p_store_scale.argtypes = [vp, vp, f32, i64, vp]
         L.p2p_latent_step.argtypes = [ctypes.POINTER(LatentArgs), vp]
+        L.p2p_plms_step.argtypes = [ctypes.POINTER(PlmsArgs), vp]
         L.p2p_attn_fwd_lse.argtypes = [ctypes.POINTER(AttnTensors), vp, vp]
         L.p2p_attn_bwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
         L.p2p_attn_bwd_workspace.argtypes = [ctypes.POINTER(AttnTensors)]
@@ -176,7 +192,7 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_attn_probs", "p2p_attn_pv", "p2p_localblend", "p2p_store_scale", "p2p_latent_step",
                     "p2p_attn_fwd_lse", "p2p_attn_bwd", "p2p_attn_bwd_workspace", "p2p_clock_probe",
                     "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu",
-                    "p2p_self_attn_kernel", "p2p_cross_attn_kernel")
+                    "p2p_self_attn_kernel", "p2p_cross_attn_kernel", "p2p_plms_step")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -438,28 +454,20 @@ def store_scale(src: torch.Tensor, divisor: float, out: Optional[torch.Tensor] =
     return out
 
 
-def latent_step(eps, x, out, coeffs, guidance=None, mask=None, group_size=0, group_blend=None, blend=None):
-    """Fused CFG + DDIM step + LocalBlend blend (p2p_latent_step).  eps: [2B or B, C, H, W]
-    (f32/bf16/f16, uncond block first when guidance is given); x, out: f32 [B, C, H, W] (out may be
-    x unless ``blend`` is given); coeffs: (sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev,
-    sqrt_one_minus_alpha_prev) floats; mask: uint8 [B, H, W] or None; group_size: prompts per
-    prompt group (0 = one group), with group_blend (uint8 [B / group_size] or None = every group)
-    selecting the groups that blend.  blend: instead of ``mask``, one entry per prompt group --
-    None (no blend) or (sums f32 [group prompts, 2, lh, res^2], th_pool, th_sub, use_substruct):
-    the folded LocalBlend word sums the mask is built from in the same launch."""
+def _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, what):
+    """The fields p2p_latent_step_args and p2p_plms_step_args share (a: LatentArgs or PlmsArgs),
+    checked and filled; returns the bytes of folded word sums the launch reads (0: no ``blend``)."""
     _require_cuda(eps, x, out, mask)
     for t in (eps, x, out):
         assert t.is_contiguous()
     assert x.dtype == torch.float32 and out.dtype == torch.float32 and x.shape == out.shape
     B, C, H, W = x.shape
     assert eps.shape[1:] == x.shape[1:] and eps.shape[0] == (2 * B if guidance is not None else B)
-    a = LatentArgs()
     a.eps, a.eps_dtype = eps.data_ptr(), _dtype_code(eps)
     a.cfg = 1 if guidance is not None else 0
     a.guidance = float(guidance) if guidance is not None else 0.0
     a.x, a.out = x.data_ptr(), out.data_ptr()
     a.n_prompts, a.channels, a.height, a.width = B, C, H, W
-    a.sqrt_beta_t, a.sqrt_alpha_t, a.sqrt_alpha_prev, a.sqrt_one_minus_alpha_prev = [float(c) for c in coeffs]
     if mask is not None:
         assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape[-2:] == (H, W)
         a.mask = mask.data_ptr()
@@ -475,10 +483,10 @@ def latent_step(eps, x, out, coeffs, guidance=None, mask=None, group_size=0, gro
     sums_bytes = 0
     if blend is not None and any(e is not None for e in blend):
         if mask is not None or group_blend is not None or out.data_ptr() == x.data_ptr():
-            raise HipError("latent_step: blend (folded sums) excludes mask / group_blend and out aliasing x")
+            raise HipError(f"{what}: blend (folded sums) excludes mask / group_blend and out aliasing x")
         gs = group_size if group_size > 0 else B
         if len(blend) != B // gs or len(blend) > MAX_GROUPS:
-            raise HipError(f"latent_step: {len(blend)} blend entries for {B // gs} prompt groups")
+            raise HipError(f"{what}: {len(blend)} blend entries for {B // gs} prompt groups")
         ref = next(e for e in blend if e is not None)
         _, th_pool, th_sub, use_sub = ref
         lh, r2 = ref[0].shape[2], ref[0].shape[3]
@@ -489,11 +497,26 @@ def latent_step(eps, x, out, coeffs, guidance=None, mask=None, group_size=0, gro
             _require_cuda(sums)
             if (sums.dtype != torch.float32 or not sums.is_contiguous() or tuple(sums.shape) != (gs, 2, lh, r2)
                     or tuple(e[1:]) != (th_pool, th_sub, use_sub)):
-                raise HipError("latent_step: blend sums must be f32 [group, 2, lh, res^2] with one threshold set")
+                raise HipError(f"{what}: blend sums must be f32 [group, 2, lh, res^2] with one threshold set")
             a.blend_sums[g] = sums.data_ptr()
             sums_bytes += sums.numel() * 4
         a.blend_lh, a.blend_res = int(lh), int(round(r2 ** 0.5))
         a.blend_th_pool, a.blend_th_sub, a.blend_sub = float(th_pool), float(th_sub), int(bool(use_sub))
+    return sums_bytes
+
+
+def latent_step(eps, x, out, coeffs, guidance=None, mask=None, group_size=0, group_blend=None, blend=None):
+    """Fused CFG + DDIM step + LocalBlend blend (p2p_latent_step).  eps: [2B or B, C, H, W]
+    (f32/bf16/f16, uncond block first when guidance is given); x, out: f32 [B, C, H, W] (out may be
+    x unless ``blend`` is given); coeffs: (sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev,
+    sqrt_one_minus_alpha_prev) floats; mask: uint8 [B, H, W] or None; group_size: prompts per
+    prompt group (0 = one group), with group_blend (uint8 [B / group_size] or None = every group)
+    selecting the groups that blend.  blend: instead of ``mask``, one entry per prompt group --
+    None (no blend) or (sums f32 [group prompts, 2, lh, res^2], th_pool, th_sub, use_substruct):
+    the folded LocalBlend word sums the mask is built from in the same launch."""
+    a = LatentArgs()
+    sums_bytes = _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, "latent_step")
+    a.sqrt_beta_t, a.sqrt_alpha_t, a.sqrt_alpha_prev, a.sqrt_one_minus_alpha_prev = [float(c) for c in coeffs]
     obs = LAUNCH_OBSERVER
     if obs is not None and hasattr(obs, "before_aux"):
         # algorithmic bytes: eps read, x read, out written, mask (or the folded word sums) read
@@ -504,6 +527,41 @@ def latent_step(eps, x, out, coeffs, guidance=None, mask=None, group_size=0, gro
     if obs is not None and hasattr(obs, "after_aux"):
         obs.after_aux("latent_blend" if sums_bytes else "latent_step")
     _check(rc, "p2p_latent_step")
+    return out
+
+
+def plms_step(eps, x, out, plan, guidance=None, mask=None, group_size=0, group_blend=None, blend=None,
+              hist=(), hist_out=None):
+    """Fused CFG + PLMS step + LocalBlend blend (p2p_plms_step): latent_step's arguments with, in
+    place of the DDIM coefficients, ``plan`` -- a pndm.StepPlan (weights, n_hist, sample_coeff,
+    eps_num, eps_den) -- and the scheduler's history: ``hist`` the stored f32 [B, C, H, W] model
+    outputs the plan reads, newest first, ``hist_out`` None or the f32 tensor that receives this
+    call's CFG-combined eps.  x is the sample the plan steps from."""
+    a = PlmsArgs()
+    sums_bytes = _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, "plms_step")
+    n_hist = int(plan.n_hist)
+    if n_hist != len(hist) or len(plan.weights) != n_hist + 1 or n_hist > 4:
+        raise HipError(f"plms_step: {len(hist)} history tensors for a plan of {n_hist} (weights {len(plan.weights)})")
+    _require_cuda(hist_out, *hist)
+    for h in tuple(hist) + ((hist_out,) if hist_out is not None else ()):
+        if h.dtype != torch.float32 or not h.is_contiguous() or h.shape != x.shape:
+            raise HipError("plms_step: history tensors must be contiguous f32 of the latent's shape")
+    for i, h in enumerate(hist):
+        a.hist[i] = h.data_ptr()
+    a.n_hist = n_hist
+    for i, w in enumerate(plan.weights):
+        a.w[i] = float(w)
+    a.hist_out = hist_out.data_ptr() if hist_out is not None else None
+    a.sample_coeff, a.eps_num, a.eps_den = float(plan.sample_coeff), float(plan.eps_num), float(plan.eps_den)
+    kind = "plms_blend" if sums_bytes else "plms_step"
+    obs = LAUNCH_OBSERVER
+    if obs is not None and hasattr(obs, "before_aux"):
+        obs.before_aux(kind, eps.numel() * eps.element_size() + (2 + n_hist + (hist_out is not None)) * x.numel() * 4 +
+                       (mask.numel() if mask is not None else 0) + sums_bytes)
+    rc = lib().p2p_plms_step(ctypes.byref(a), _stream(x.device))
+    if obs is not None and hasattr(obs, "after_aux"):
+        obs.after_aux(kind)
+    _check(rc, "p2p_plms_step")
     return out
 
 

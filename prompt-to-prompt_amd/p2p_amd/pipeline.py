@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from .ddim import DDIMScheduler
+from .pndm import PNDMScheduler
 from .tokenizer import default_tokenizer
 from .unet import UNet2DConditionModel
 
@@ -34,16 +35,26 @@ class SyntheticTextEncoder(nn.Module):
 
 
 class SyntheticStableDiffusion:
-    def __init__(self, device="cuda", dtype=torch.float32, seed=0):
+    """``scheduler``: "ddim" (null_text.py:16-20) or "pndm" (the PLMS sampler the v1.4 pipeline of
+    main.py:29 carries: skip_prk_steps, steps_offset 1).  ``unet_config``: keyword arguments of the
+    U-Net in place of the SD-v1.4 shape (tests run a narrow one)."""
+
+    def __init__(self, device="cuda", dtype=torch.float32, seed=0, scheduler="ddim", unet_config=None):
         self.device = torch.device(device)
         self.tokenizer = default_tokenizer()
         torch.manual_seed(seed)
-        self.unet = UNet2DConditionModel().to(self.device, dtype).eval()
+        self.unet = UNet2DConditionModel(**(unet_config or {})).to(self.device, dtype).eval()
         for p in self.unet.parameters():
             p.requires_grad_(False)
         self.text_encoder = SyntheticTextEncoder().to(self.device)
-        self.scheduler = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                                       clip_sample=False, set_alpha_to_one=False)
+        if scheduler == "ddim":
+            self.scheduler = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                                           clip_sample=False, set_alpha_to_one=False)
+        elif scheduler == "pndm":
+            self.scheduler = PNDMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                                           set_alpha_to_one=False, skip_prk_steps=True, steps_offset=1)
+        else:
+            raise ValueError(f"scheduler {scheduler!r}: 'ddim' or 'pndm'")
         self.vae = None
 
 

@@ -22,9 +22,9 @@ from .ptp_words import get_time_words_attention_alpha, get_word_inds, update_alp
 
 # ------------------------------------------------------------------ sampling loop
 def diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource=False, t_unet=None):
-    """One CFG denoising step (ptp_utils.py:65-76).  With this library's DDIM scheduler and a
-    controller whose step_callback is its own, the CFG combine, the DDIM step and LocalBlend's
-    latent blend run as one HIP kernel (p2p_latent_step) -- same result, bit for bit.
+    """One CFG denoising step (ptp_utils.py:65-76).  With this library's DDIM or PNDM scheduler and a
+    controller whose step_callback is its own, the CFG combine, the scheduler's step and LocalBlend's
+    latent blend run as one HIP kernel (p2p_latent_step / p2p_plms_step) -- same result, bit for bit.
     ``t_unet``: the same timestep as a device tensor for the U-Net (a captured step must not copy
     a host timestep to the device); the scheduler keeps reading the host ``t``."""
     tu = t if t_unet is None else t_unet
@@ -46,7 +46,9 @@ def diffusion_step(model, controller, latents, context, t, guidance_scale, low_r
 def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale):
     from . import _hip
     from .ddim import DDIMScheduler
-    if not (isinstance(model.scheduler, DDIMScheduler) and latents.is_cuda and latents.dtype == torch.float32
+    from .pndm import PNDMScheduler
+    sched = model.scheduler
+    if not (isinstance(sched, (DDIMScheduler, PNDMScheduler)) and latents.is_cuda and latents.dtype == torch.float32
             and eps_u.dtype in (torch.float32, torch.bfloat16, torch.float16) and hasattr(controller, "fused_step_mask")):
         return None
     ok, mask_fn = controller.fused_step_mask()
@@ -57,11 +59,22 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
     from .controllers import FoldedBlendMask, group_mask_tensor
     x = latents.contiguous()
     out = torch.empty_like(x)
+    plms = isinstance(sched, PNDMScheduler)
+    if plms:
+        # the call's plan (pndm.plan_step, which the eager step executes too): the sample it steps
+        # from -- call 0's on the corrector call, kept by reference, hence the fresh ``out`` -- the
+        # stored model outputs it reads and the ring buffer that receives this call's
+        plan = sched.plan_step(t)
+        src = sched.step_source(plan, x).contiguous()
+        hist, hist_out = sched.history(plan), sched.history_slot(plan, x)
+    else:
+        src, hist, hist_out = x, (), None
     mask = mask_fn(tuple(x.shape[2:])) if mask_fn is not None else None
     group_size, group_blend, blend = 0, None, None
     folded = mask if isinstance(mask, FoldedBlendMask) else (
         next((m for m in mask[0] if m is not None), None) if isinstance(mask, tuple) and len(mask) == 2 else None)
-    if folded is not None and not _blend_launch_ok(x, out, eps, folded):
+    kept = hist + ((hist_out,) if hist_out is not None else ())
+    if folded is not None and not _blend_launch_ok(src, out, eps, folded, kept):
         # shapes the one-launch LocalBlend does not take: the mask is built by p2p_localblend and
         # the latent step reads it (the same mask, two launches)
         mask = folded.materialize() if isinstance(mask, FoldedBlendMask) else group_mask_tensor(
@@ -73,18 +86,24 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
         mask, group_size = None, mask[1]
     elif isinstance(mask, tuple):          # prompt-group batch: (mask, group size, groups that blend)
         mask, group_size, group_blend = mask
-    return _hip.latent_step(eps, x, out, model.scheduler.prev_coeffs(t), guidance_scale, mask,
-                            group_size, group_blend, blend)
+    if not plms:
+        return _hip.latent_step(eps, x, out, sched.prev_coeffs(t), guidance_scale, mask, group_size, group_blend, blend)
+    _hip.plms_step(eps, src, out, plan, guidance_scale, mask, group_size, group_blend, blend, hist, hist_out)
+    sched.commit(plan, hist_out, x)
+    return out
 
 
-def _blend_launch_ok(x, out, eps, folded) -> bool:
+def _blend_launch_ok(x, out, eps, folded, more=()) -> bool:
     """The one-launch LocalBlend's preconditions (p2p_blend.hip run_latent_step, include/p2p_hip.h):
-    whole 4-pixel vectors (H*W % 4 == 0), 16-byte aligned x / out / eps, and a latent at least as
-    large as the map resolution (the 3x3-pooled map is nearest-upsampled onto it)."""
+    whole 4-pixel vectors (H*W % 4 == 0), 16-byte aligned x / out / eps (and ``more``: the PLMS
+    history tensors), and a latent at least as large as the map resolution (the 3x3-pooled map is
+    nearest-upsampled onto it)."""
     H, W = x.shape[2], x.shape[3]
     res = int(round(folded.sums.shape[-1] ** 0.5))
-    return ((H * W) % 4 == 0 and res <= H and res <= W and res * res <= 256
-            and (x.data_ptr() | out.data_ptr() | eps.data_ptr()) % 16 == 0)
+    ptrs = x.data_ptr() | out.data_ptr() | eps.data_ptr()
+    for t in more:
+        ptrs |= t.data_ptr()
+    return (H * W) % 4 == 0 and res <= H and res <= W and res * res <= 256 and ptrs % 16 == 0
 
 
 def latent2image(vae, latents):

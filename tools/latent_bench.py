@@ -3,6 +3,8 @@ B = 4 prompts, 4 x 64 x 64 latents, bf16 eps, folded word sums [4, 2, 40, 256]:
   fused     : p2p_latent_step with blend sums (latent_blend_kernel: mask + blend + CFG + DDIM)
   two_step  : p2p_localblend mask (blend_finalize_kernel) + p2p_latent_step with the mask
   plain     : p2p_latent_step without a blend
+  plms_*    : the same two one-launch / plain forms of p2p_plms_step at a call >= 4 (three stored eps
+              read, the new one written)
 Usage: python tools/latent_bench.py [iters]   (run under rocprofv3 --kernel-trace --stats for kernel times)"""
 import json
 import os
@@ -49,6 +51,16 @@ def main(iters=200):
          "two_step_us": timed(lambda: _hip.latent_step(eps, x, out, coeffs, 7.5, fm.materialize()), iters),
          "mask_only_us": timed(lambda: fm.materialize(), iters),
          "plain_us": timed(lambda: _hip.latent_step(eps, x, out, coeffs, 7.5, None), iters)}
+    from p2p_amd.pndm import PNDMScheduler
+    p = PNDMScheduler()
+    p.set_timesteps(50)
+    for t in p.timesteps.tolist()[:5]:      # the state of call 5: three stored outputs are read
+        p.step(torch.randn(B, 4, 64, 64, device=dev, generator=g), t, x)
+    plan = p.plan_step(int(p.timesteps[5]))
+    hist, slot = p.history(plan), p.history_slot(plan, x)
+    r["plms_fused_us"] = timed(lambda: _hip.plms_step(eps, x, out, plan, 7.5, None, 0, None, [fm.latent_entry()],
+                                                      hist=hist, hist_out=slot), iters)
+    r["plms_plain_us"] = timed(lambda: _hip.plms_step(eps, x, out, plan, 7.5, None, hist=hist, hist_out=slot), iters)
     print(json.dumps({k: round(v, 2) for k, v in r.items()}), flush=True)
 
 
