@@ -334,7 +334,10 @@ typedef struct {
   const void* gamma;        /* [channels]                                                   */
   const void* beta;         /* [channels]                                                   */
   void* y;
-  float* stats;             /* workspace [n * groups * 2] f32 ({mean, rstd} per slab)       */
+  float* stats;             /* workspace, p2p_group_norm_stats_floats() f32: {mean, rstd} per
+                             * slab -- n * groups * 2, all of it for slabs (channels / groups *
+                             * hw) below 262,144 elements -- then, from that size, the
+                             * per-chunk partials of the split statistics                    */
   int32_t n, channels, hw, groups;
   float eps;
   int32_t act;              /* P2P_ACT_*                                                    */
@@ -343,6 +346,9 @@ typedef struct {
 } p2p_group_norm_args;
 
 int p2p_group_norm(const p2p_group_norm_args* a, p2p_stream_t stream);
+/* f32 elements p2p_group_norm needs behind `stats` for these sizes (a function of the sizes only),
+ * or P2P_E_ARG. */
+int64_t p2p_group_norm_stats_floats(int32_t n, int32_t channels, int32_t hw, int32_t groups);
 
 /* out[n, c, hw] = a[n, c, hw] + b + bias[c] + bias2[c]: the residual add of ResnetBlock2D with the
  * biases of conv2 and of the shortcut conv (b NCHW), and of Transformer2DModel (b = the proj_out
@@ -371,6 +377,34 @@ typedef struct {
 } p2p_geglu_args;
 
 int p2p_geglu(const p2p_geglu_args* a, p2p_stream_t stream);
+
+/* The image ends of the pipeline (additive to ABI 16; p2p_amd/ptp_utils.py latent2image /
+ * image2latent).  Three channels.  dtype: P2P_DTYPE_F32 / BF16 / F16, anything else is
+ * P2P_E_DTYPE.  Both take height * width % 4 == 0 only (four pixels per thread, no scalar tail)
+ * and answer P2P_E_ALIGN otherwise, as for a float pointer off 16 bytes or a byte pointer off 4:
+ * the caller then converts some other way. */
+
+/* out[n, y, x, c] = uint8(clamp(x[n, c, y, x] / 2 + 0.5, 0, 1) * 255), truncating: the reference's
+ * latent2image arithmetic in f32, every operation rounded on its own, so the bytes equal
+ * (((x.float() / 2 + 0.5).clamp(0, 1)) * 255).to(torch.uint8). */
+typedef struct {
+  const void* x;   /* [n, 3, height, width], dense */
+  uint8_t* out;    /* [n, height, width, 3]        */
+  int32_t n, height, width;
+  int32_t dtype;   /* of x                         */
+} p2p_image_u8_args;
+
+int p2p_image_u8(const p2p_image_u8_args* a, p2p_stream_t stream);
+
+/* out[n, c, y, x] = img[n, y, x, c] / 127.5 - 1, computed in f32 and rounded once to dtype. */
+typedef struct {
+  const uint8_t* img; /* [n, height, width, 3], dense */
+  void* out;          /* [n, 3, height, width]        */
+  int32_t n, height, width;
+  int32_t dtype;      /* of out                       */
+} p2p_image_to_model_args;
+
+int p2p_image_to_model(const p2p_image_to_model_args* a, p2p_stream_t stream);
 
 /* Measurement only (ABI 15; bench.py's roofline clock, not part of the reference's interface):
  * n_workgroups one-wave workgroups each read the shader-cycle counter and the constant 100 MHz

@@ -331,6 +331,7 @@ int p2p_attn_fwd_lse(const p2p_attn_tensors* t, float* lse, p2p_stream_t stream)
 int64_t p2p_attn_bwd_workspace(const p2p_attn_tensors* t) {
   if (!t || t->n_batch < 1 || t->n_query < 1 || t->n_key < 1 || t->n_heads < 1 || t->head_dim < 1) return 0;
   if (t->io_dtype == P2P_DTYPE_F16) return P2P_E_DTYPE;   // no fp16 backward (p2p_attn_bwd rejects it too)
+  if (t->head_dim == kWideHeadDim) return P2P_E_HEAD_DIM;  // forward only (p2p_attn_bwd rejects it too)
   const int split = bwd_kv_split(t->n_batch, t->n_heads, t->n_query, t->n_key, t->head_dim);
   if (split <= 1) return 0;
   return (int64_t)2 * split * t->n_batch * t->n_key * t->n_heads * t->head_dim * (int64_t)sizeof(float);
@@ -390,6 +391,11 @@ int p2p_group_norm(const p2p_group_norm_args* a, p2p_stream_t stream) {
   return run_group_norm(*a, (hipStream_t)stream);
 }
 
+int64_t p2p_group_norm_stats_floats(int32_t n, int32_t channels, int32_t hw, int32_t groups) {
+  if (n < 1 || channels < 1 || hw < 1 || groups < 1 || channels % groups) return P2P_E_ARG;
+  return gn_stats_floats((int64_t)n * groups, (int64_t)(channels / groups) * hw);
+}
+
 int p2p_bias_residual(const p2p_bias_residual_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
   return run_bias_residual(*a, (hipStream_t)stream);
@@ -398,6 +404,16 @@ int p2p_bias_residual(const p2p_bias_residual_args* a, p2p_stream_t stream) {
 int p2p_geglu(const p2p_geglu_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
   return run_geglu(*a, (hipStream_t)stream);
+}
+
+int p2p_image_u8(const p2p_image_u8_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_image_u8(*a, (hipStream_t)stream);
+}
+
+int p2p_image_to_model(const p2p_image_to_model_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_image_to_model(*a, (hipStream_t)stream);
 }
 
 int p2p_clock_probe(uint64_t* out, int32_t n_workgroups, int32_t ticks, p2p_stream_t stream) {

@@ -14,6 +14,7 @@ int run_self(const SelfArgs& a, int io_dtype, int compute, int d, int mode, hipS
     case FAM_SPLIT:
     case FAM_HALVES:
     case FAM_RING: return launch_self_split(a, k, st);
+    case FAM_WIDE: return launch_self_wide(a, select_precision(io_dtype, compute), st);
     default: return launch_self_fused(a, select_precision(io_dtype, compute), d, k, st);
   }
 }

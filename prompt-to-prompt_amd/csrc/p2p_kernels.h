@@ -115,6 +115,8 @@ int launch_self_multi(const SelfArgs& a, SelfKernel k, hipStream_t st);
 int launch_self40(const SelfArgs& a, SelfKernel k, hipStream_t st);
 // self_split_kernel / self_halves_kernel / self_ring_kernel (p2p_selfsplit.hip): d = 160, bf16, O only
 int launch_self_split(const SelfArgs& a, SelfKernel k, hipStream_t st);
+// self_wide_kernel (p2p_selfwide.hip): d = 512, bf16 / fp16 inputs, O only
+int launch_self_wide(const SelfArgs& a, int prec, hipStream_t st);
 // AttentionStore epilogue of the self layers whose maps are kept (p2p_selfmaps.hip): p = exp2(c s -
 // lse) for the entries a.map_entry[0 .. n_maps) (a.lse filled by a preceding MODE_FUSED_ launch)
 int run_self_maps(const SelfArgs& a, int io_dtype, int compute, int d, hipStream_t st);
@@ -148,9 +150,33 @@ int bwd_kv_split(int N, int H, int P, int K, int d);   // launcher's query split
 int run_store_scale(const float* src, float* dst, float divisor, int64_t n, hipStream_t st);
 // U-Net glue (p2p_unet.hip): every argument check happens in these, before the first launch
 constexpr int64_t kGnStatsWide = 32768;   // slab elements from which the statistics kernel runs 1024 threads
+// Slab elements from which the statistics run in the split form (one workgroup per chunk, then a
+// combine launch).  It has to lie strictly above the U-Net's largest slab, 30 channels x 4096
+// pixels = 122,880 elements, so that every U-Net launch stays on gn_stats_kernel and keeps its bits.
+// Timed against the one-workgroup form on the VAE decoder's norms (statistics + apply, same box,
+// runs alternated, profiles/r09/vae/gn_stats.txt): 262,144 elements 34.1 -> 22.1 us, 524,288
+// 58.2 -> 33.3, 1,048,576 130 -> 55, 2,097,152 246 -> 97; the split form is taken from the smallest
+// of these (sizes between it and 122,880 do not occur in the VAE and were not timed).
+constexpr int64_t kGnStatsSplit = 262144;
+constexpr int64_t kGnStatsChunk = 32768;   // target elements per chunk (a 1024-thread sweep, as kGnStatsWide)
+constexpr int kGnStatsMaxChunks = 256;
+// chunks of a slab: a function of its size only (never of the device), 1 = the one-workgroup form
+constexpr int gn_stats_chunks(int64_t slab) {
+  if (slab < kGnStatsSplit) return 1;
+  const int64_t c = (slab + kGnStatsChunk - 1) / kGnStatsChunk;
+  return (int)(c > kGnStatsMaxChunks ? kGnStatsMaxChunks : c);
+}
+// f32 elements of p2p_group_norm_args.stats: {mean, rstd} per slab, then the split form's partials
+constexpr int64_t gn_stats_floats(int64_t slabs, int64_t slab) {
+  const int c = gn_stats_chunks(slab);
+  return slabs * 2 + (c > 1 ? slabs * c * 3 : 0);
+}
 int run_group_norm(const p2p_group_norm_args& a, hipStream_t st);
 int run_bias_residual(const p2p_bias_residual_args& a, hipStream_t st);
 int run_geglu(const p2p_geglu_args& a, hipStream_t st);
+// the image ends (p2p_image.hip): every argument check happens in these, before the launch
+int run_image_u8(const p2p_image_u8_args& a, hipStream_t st);
+int run_image_to_model(const p2p_image_to_model_args& a, hipStream_t st);
 int run_clock_probe(unsigned long long* out, int n_wg, int ticks, hipStream_t st);
 
 }  // namespace p2p

@@ -40,9 +40,12 @@ inline bool head_dim_compiled(int d) {
   }
 }
 
+// the one head dim outside that list: self_wide_kernel only (select_self)
+constexpr int kWideHeadDim = 512;
+
 // ---------------------------------------------------------------------------- self attention
 // family of a self kernel form: which file's launcher takes it
-enum SelfFamily { FAM_FUSED, FAM_PV, FAM_MULTI, FAM_SELF40, FAM_SPLIT, FAM_HALVES, FAM_RING };
+enum SelfFamily { FAM_FUSED, FAM_PV, FAM_MULTI, FAM_SELF40, FAM_SPLIT, FAM_HALVES, FAM_RING, FAM_WIDE };
 // row-statistics form of self_attn_fused_kernel
 enum SelfForm { FORM_DEFAULT, FORM_EXACT, FORM_NOMAX };
 
@@ -83,7 +86,8 @@ enum SelfForm { FORM_DEFAULT, FORM_EXACT, FORM_NOMAX };
   X(SELF_SPLIT_3x2, FAM_SPLIT, 2, 3, FORM_DEFAULT, "self_split_kernel<160,3,2>")                         \
   X(SELF_SPLIT_4x2, FAM_SPLIT, 2, 4, FORM_DEFAULT, "self_split_kernel<160,4,2>")                         \
   X(SELF_HALVES, FAM_HALVES, 32, 4, FORM_DEFAULT, "self_halves_kernel")                                  \
-  X(SELF_RING, FAM_RING, 32, 4, FORM_DEFAULT, "self_ring_kernel<160,4>")
+  X(SELF_RING, FAM_RING, 32, 4, FORM_DEFAULT, "self_ring_kernel<160,4>")                                 \
+  X(SELF_WIDE, FAM_WIDE, 64, 4, FORM_DEFAULT, "self_wide_kernel<512,…>")
 
 enum SelfKernel {
 #define P2P_ENUM(id, fam, bk, w, form, nm) id,
@@ -150,6 +154,12 @@ inline int select_self(int io_dtype, int compute, int d, int P, int K, int mode,
                        int variant) {
   const int prec = select_precision(io_dtype, compute);
   if (prec < 0) return prec;
+  // d = 512 (the VAE's mid-block attention, one head as wide as the layer): p2p_selfwide.hip, the
+  // only kernel of that width -- bf16 / fp16 inputs, O only.  512 is not in P2P_FOR_EACH_D, so
+  // everything else at d = 512 (f32 inputs, check mode, P V mode, lse, kept maps, cross) is an
+  // uncompiled head dim like any other.
+  if (d == kWideHeadDim && mode == MODE_FUSED_ && !lse && !maps && (prec == PREC_BF16 || prec == PREC_F16))
+    return SELF_WIDE;
   if (!head_dim_compiled(d)) return P2P_E_HEAD_DIM;
   (void)variant;
   if (mode == MODE_PV_) return fused_bk(d, prec != PREC_F32) == 32 ? SELF_PV_32x4 : SELF_PV_64x4;

@@ -3,11 +3,18 @@
 // GEGLU.  16-bit I/O (bf16 or f16), f32 arithmetic, one rounding at the store; every reduction
 // runs in a fixed order (no atomics), so two launches on the same input are bit-identical.
 //
-// GroupNorm is two launches: gn_stats_kernel reads each (n, group) slab twice -- mean, then the
+// GroupNorm is two launches (three for the VAE's large slabs, below): gn_stats_kernel reads each (n, group) slab twice -- mean, then the
 // centred sum of squares; the second sweep of the <= 245 KB slab hits the L2 -- and leaves
 // {mean, rstd} in a caller-owned workspace; the apply kernel is then tiled freely over the whole
 // tensor (the slab count n x groups says nothing about its grid), which is what lets the
 // token-major store go through an LDS transpose with 128-byte runs per pixel.
+//
+// Slabs of kGnStatsSplit elements or more (p2p_kernels.h; the VAE's, up to 2 M elements with as few as
+// 32 slabs per launch) take the split form instead: gn_stats_split_kernel runs one workgroup per
+// chunk of a slab -- gn_stats_chunks(slab) equal chunks, a function of the slab size only -- and
+// leaves {count, mean, M2} per chunk behind the {mean, rstd} pairs of the workspace;
+// gn_stats_combine_kernel then folds each slab's partials in chunk order with Chan's formula.  No
+// atomics, the same order on every launch: bit-identical from launch to launch as well.
 #include "p2p_device.h"
 #include "p2p_kernels.h"
 
@@ -85,6 +92,79 @@ __global__ void gn_stats_kernel(p2p_group_norm_args a) {
     a.stats[2 * blockIdx.x] = mean;
     a.stats[2 * blockIdx.x + 1] = 1.f / sqrtf(var + a.eps);
   }
+}
+
+// one workgroup per (slab, chunk): the chunk's count, mean and centred sum of squares (two sweeps
+// of <= 64 KB), to part[(slab * chunks + chunk) * 3 ..]
+template <bool F16>
+__global__ __launch_bounds__(1024) void gn_stats_split_kernel(p2p_group_norm_args a, int chunks, int vpc) {
+  __shared__ float red[16];
+  const int G = a.groups, C = a.channels, cpg = C / G;
+  const int slab_id = blockIdx.x / chunks, chunk = blockIdx.x - slab_id * chunks;
+  const int n = slab_id / G, g = slab_id - n * G;
+  const int hwv = a.hw >> 3;
+  const int nv = cpg * hwv;
+  const int v0 = chunk * vpc;
+  const int v1 = min(nv, v0 + vpc);
+  const int64_t row0 = (int64_t)n * C + g * cpg;
+  const u16x8_t* x = reinterpret_cast<const u16x8_t*>(static_cast<const uint16_t*>(a.x) + row0 * a.hw);
+  const uint16_t* add = static_cast<const uint16_t*>(a.chan_add);
+  const uint16_t* bias = static_cast<const uint16_t*>(a.chan_bias);
+  if (add) add += (int64_t)n * a.chan_add_stride + g * cpg;
+  if (bias) bias += g * cpg;
+  const bool shifted = add || bias;
+  auto chan_shift = [&](int iv) {
+    const int c = iv / hwv;
+    return (add ? ld16<F16>(add[c]) : 0.f) + (bias ? ld16<F16>(bias[c]) : 0.f);
+  };
+  const float cnt = 8.f * (float)max(v1 - v0, 0);
+  float s = 0.f;
+  for (int iv = v0 + threadIdx.x; iv < v1; iv += blockDim.x) {
+    const u16x8_t v = x[iv];
+    float t = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t += ld16<F16>(v[j]);
+    if (shifted) t += 8.f * chan_shift(iv);
+    s += t;
+  }
+  const float mean = cnt > 0.f ? block_sum(s, red) / cnt : 0.f;
+  float q = 0.f;
+  for (int iv = v0 + threadIdx.x; iv < v1; iv += blockDim.x) {
+    const u16x8_t v = x[iv];
+    const float m = shifted ? mean - chan_shift(iv) : mean;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = ld16<F16>(v[j]) - m;
+      q += d * d;
+    }
+  }
+  const float m2 = block_sum(q, red);
+  if (threadIdx.x == 0) {
+    float* const part = a.stats + 2 * (int64_t)a.n * G + (int64_t)blockIdx.x * 3;
+    part[0] = cnt;
+    part[1] = mean;
+    part[2] = m2;
+  }
+}
+
+// one thread per slab: Chan's pairwise update over the chunks, in chunk order
+__global__ __launch_bounds__(256) void gn_stats_combine_kernel(p2p_group_norm_args a, int chunks) {
+  const int slab_id = blockIdx.x * 256 + threadIdx.x;
+  const int slabs = a.n * a.groups;
+  if (slab_id >= slabs) return;
+  const float* part = a.stats + 2 * (int64_t)slabs + (int64_t)slab_id * chunks * 3;
+  float cnt = 0.f, mean = 0.f, m2 = 0.f;
+  for (int c = 0; c < chunks; ++c) {
+    const float nb = part[3 * c], mb = part[3 * c + 1], qb = part[3 * c + 2];
+    if (nb == 0.f) continue;
+    const float tot = cnt + nb;
+    const float delta = mb - mean;
+    mean += delta * (nb / tot);
+    m2 += qb + delta * delta * (cnt * (nb / tot));
+    cnt = tot;
+  }
+  a.stats[2 * slab_id] = mean;
+  a.stats[2 * slab_id + 1] = 1.f / sqrtf(m2 / cnt + a.eps);
 }
 
 // what one channel of one batch entry needs: y = ((x + shift) - mean) * rstd * gamma + beta
@@ -253,8 +333,17 @@ template <bool F16>
 void launch_group_norm(const p2p_group_norm_args& a, hipStream_t st) {
   // a slab of at least kGnStatsWide elements takes 1024 threads, a smaller one 256
   const int64_t slab = (int64_t)(a.channels / a.groups) * a.hw;
-  launch_kernel(gn_stats_kernel<F16>, dim3((unsigned)(a.n * a.groups)), dim3(slab >= kGnStatsWide ? 1024 : 256), 0,
-                st, a);
+  const int chunks = gn_stats_chunks(slab);
+  if (chunks > 1) {
+    const int nv = (int)(slab / 8);
+    const int vpc = (nv + chunks - 1) / chunks;   // 8-element vectors per chunk (the last may hold fewer)
+    launch_kernel(gn_stats_split_kernel<F16>, dim3((unsigned)(a.n * a.groups * chunks)), dim3(1024), 0, st, a, chunks,
+                  vpc);
+    launch_kernel(gn_stats_combine_kernel, dim3((unsigned)((a.n * a.groups + 255) / 256)), dim3(256), 0, st, a, chunks);
+  } else {
+    launch_kernel(gn_stats_kernel<F16>, dim3((unsigned)(a.n * a.groups)), dim3(slab >= kGnStatsWide ? 1024 : 256), 0,
+                  st, a);
+  }
   const bool act = a.act == P2P_ACT_SILU;
   if (a.y_layout == P2P_LAYOUT_NCHW) {
     const int64_t n_vec = (int64_t)a.n * a.channels * a.hw / 8;
@@ -285,6 +374,10 @@ int run_group_norm(const p2p_group_norm_args& a, hipStream_t st) {
   if (!a.x || !a.gamma || !a.beta || !a.y || !a.stats) return P2P_E_ARG;
   if (a.n < 1 || a.channels < 1 || a.hw < 1 || a.groups < 1 || a.channels % a.groups) return P2P_E_ARG;
   if (a.n > 65535 || (int64_t)a.n * a.groups > INT32_MAX / 2) return P2P_E_ARG;
+  // the statistics kernels index a slab's 8-element vectors, and the split form's grid, in 32 bits
+  if ((int64_t)(a.channels / a.groups) * a.hw > INT32_MAX ||
+      (int64_t)a.n * a.groups * gn_stats_chunks((int64_t)(a.channels / a.groups) * a.hw) > INT32_MAX / 4)
+    return P2P_E_ARG;
   if (a.chan_add && a.chan_add_stride != 0 && a.chan_add_stride != a.channels) return P2P_E_ARG;
   if (a.act != P2P_ACT_NONE && a.act != P2P_ACT_SILU) return P2P_E_ARG;
   if (a.y_layout != P2P_LAYOUT_NCHW && a.y_layout != P2P_LAYOUT_TOKENS) return P2P_E_ARG;

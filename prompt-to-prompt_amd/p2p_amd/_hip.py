@@ -41,7 +41,11 @@ GROUP_F_SHARED_KV = 4   # p2p_group.flags: every entry of the group has the firs
 
 
 class HipError(RuntimeError):
-    pass
+    """``code``: the library's P2P_E_* (or HIP) code, where a rejected call raised this."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 class AttnTensors(ctypes.Structure):
@@ -130,6 +134,20 @@ class GegluArgs(ctypes.Structure):
     ]
 
 
+class ImageU8Args(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("out", ctypes.c_void_p), ("n", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("width", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
+class ImageToModelArgs(ctypes.Structure):
+    _fields_ = [
+        ("img", ctypes.c_void_p), ("out", ctypes.c_void_p), ("n", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("width", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -145,7 +163,7 @@ def lib():
         # every export returns int, but for these
         other = {"p2p_error_string": ctypes.c_char_p, "p2p_source_hash": ctypes.c_char_p,
                  "p2p_self_attn_kernel": ctypes.c_char_p, "p2p_cross_attn_kernel": ctypes.c_char_p,
-                 "p2p_attn_bwd_workspace": ctypes.c_int64}
+                 "p2p_attn_bwd_workspace": ctypes.c_int64, "p2p_group_norm_stats_floats": ctypes.c_int64}
         for fn in EXPORTED_SYMBOLS:
             getattr(L, fn).restype = other.get(fn, ctypes.c_int)
         L.p2p_error_string.argtypes = [ctypes.c_int]
@@ -163,8 +181,11 @@ def lib():
         L.p2p_attn_bwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
         L.p2p_attn_bwd_workspace.argtypes = [ctypes.POINTER(AttnTensors)]
         L.p2p_group_norm.argtypes = [ctypes.POINTER(GroupNormArgs), vp]
+        L.p2p_group_norm_stats_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_bias_residual.argtypes = [ctypes.POINTER(BiasResidualArgs), vp]
         L.p2p_geglu.argtypes = [ctypes.POINTER(GegluArgs), vp]
+        L.p2p_image_u8.argtypes = [ctypes.POINTER(ImageU8Args), vp]
+        L.p2p_image_to_model.argtypes = [ctypes.POINTER(ImageToModelArgs), vp]
         L.p2p_clock_probe.argtypes = [vp, i32, i32, vp]
         L.p2p_set_launch_events.argtypes = [vp, vp]
         if L.p2p_abi_version() != ABI_VERSION:
@@ -192,7 +213,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_attn_probs", "p2p_attn_pv", "p2p_localblend", "p2p_store_scale", "p2p_latent_step",
                     "p2p_attn_fwd_lse", "p2p_attn_bwd", "p2p_attn_bwd_workspace", "p2p_clock_probe",
                     "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu",
-                    "p2p_self_attn_kernel", "p2p_cross_attn_kernel", "p2p_plms_step")
+                    "p2p_self_attn_kernel", "p2p_cross_attn_kernel", "p2p_plms_step", "p2p_image_u8",
+                    "p2p_image_to_model", "p2p_group_norm_stats_floats")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -209,7 +231,7 @@ def clock_probe(out: torch.Tensor, ticks: int = 1000):
 def _check(rc: int, what: str):
     if rc != 0:
         msg = lib().p2p_error_string(rc).decode()
-        raise HipError(f"{what} failed: {msg} (code {rc})")
+        raise HipError(f"{what} failed: {msg} (code {rc})", rc)
 
 
 def _stream(device: torch.device) -> int:
@@ -596,7 +618,7 @@ def attn_bwd(q, k, v, o, dout, lse, heads, scale, dq, dk, dv, delta, workspace=N
 # -- U-Net glue (p2p_unet.hip).  Each returns its output, or None when the library reports the
 # arguments unsupported (dtype, alignment) or the tensors are not dense: the caller then runs
 # its torch lines.  Any other rejection raises.
-P2P_E_DTYPE, P2P_E_ALIGN = -3, -6
+P2P_E_HEAD_DIM, P2P_E_DTYPE, P2P_E_ALIGN = -2, -3, -6
 ACT_NONE, ACT_SILU = 0, 1
 LAYOUT_NCHW, LAYOUT_TOKENS = 0, 1
 
@@ -639,7 +661,11 @@ def group_norm(x, gamma, beta, groups: int, eps: float, silu: bool = False, toke
         a.chan_bias = _vec(chan_bias, x, C).data_ptr()
     a.gamma, a.beta = _vec(gamma, x, C).data_ptr(), _vec(beta, x, C).data_ptr()
     y = x.new_empty((N, H * W, C) if tokens else (N, C, H, W))
-    stats = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
+    if groups < 1 or C % groups:
+        raise HipError(f"group_norm: {C} channels in {groups} groups")
+    # {mean, rstd} per slab, and the per-chunk partials of the split statistics for large slabs
+    n_stats = int(lib().p2p_group_norm_stats_floats(N, C, H * W, int(groups)))
+    stats = torch.empty(max(n_stats, N * groups * 2), dtype=torch.float32, device=x.device)
     a.y, a.stats = y.data_ptr(), stats.data_ptr()
     a.n, a.channels, a.hw, a.groups = N, C, H * W, int(groups)
     a.eps = float(eps)
@@ -687,3 +713,40 @@ def geglu(x):
     g.rows, g.d = x2.shape[0], D
     g.dtype = _glue_dtype(x)
     return out if _glue_rc(lib().p2p_geglu(ctypes.byref(g), _stream(x.device)), "p2p_geglu") else None
+
+
+# -- the image ends (p2p_image.hip).  As the glue above: None where the library reports the shape
+# or alignment unsupported (height * width % 4 != 0), and the caller runs its torch lines.
+def image_u8(x: torch.Tensor):
+    """uint8 [N, H, W, 3] from a decoder output x [N, 3, H, W] (f32 / bf16 / f16), byte for byte
+    (((x.float() / 2 + 0.5).clamp(0, 1)) * 255).to(torch.uint8) in NHWC (p2p_image_u8)."""
+    _require_cuda(x)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise HipError(f"image_u8 needs [N, 3, H, W], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        return None
+    N, _, H, W = x.shape
+    out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=x.device)
+    a = ImageU8Args()
+    a.x, a.out = x.data_ptr(), out.data_ptr()
+    a.n, a.height, a.width, a.dtype = N, H, W, _dtype_code(x)
+    return out if _glue_rc(lib().p2p_image_u8(ctypes.byref(a), _stream(x.device)), "p2p_image_u8") else None
+
+
+def image_to_model(img: torch.Tensor, dtype: torch.dtype):
+    """[N, 3, H, W] in ``dtype`` from uint8 pixels [H, W, 3] or [N, H, W, 3]: img / 127.5 - 1 in f32,
+    rounded once (p2p_image_to_model)."""
+    _require_cuda(img)
+    if img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3:
+        raise HipError(f"image_to_model needs uint8 [H, W, 3] or [N, H, W, 3], got {img.dtype} {tuple(img.shape)}")
+    if img.dim() == 3:
+        img = img[None]
+    if not img.is_contiguous():
+        return None
+    N, H, W, _ = img.shape
+    out = torch.empty((N, 3, H, W), dtype=dtype, device=img.device)
+    a = ImageToModelArgs()
+    a.img, a.out = img.data_ptr(), out.data_ptr()
+    a.n, a.height, a.width, a.dtype = N, H, W, _dtype_code(out)
+    ok = _glue_rc(lib().p2p_image_to_model(ctypes.byref(a), _stream(img.device)), "p2p_image_to_model")
+    return out if ok else None

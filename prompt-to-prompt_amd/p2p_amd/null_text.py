@@ -219,8 +219,8 @@ class NullInversion:
     back-propagates through all 32 patched attentions: the hook is installed with no controller
     (null_text.py:610), whose plain path is differentiable on the HIP kernels
     (attention._AttentionFn: p2p_attn_fwd_lse / p2p_attn_bwd).  ``invert`` also takes the image
-    latent itself ([1, 4, H/8, W/8], the form the reference's ``image2latent`` passes through):
-    the synthetic pipeline has no VAE."""
+    latent itself ([1, 4, H/8, W/8], the form the reference's ``image2latent`` passes through),
+    which is the only form a model without a VAE (the default) can invert."""
 
     def __init__(self, model, num_ddim_steps: int = NUM_DDIM_STEPS, guidance_scale: float = GUIDANCE_SCALE,
                  use_graphs: bool = True):
@@ -261,8 +261,8 @@ class NullInversion:
             return None
         image = vae.decode(1 / 0.18215 * latents.detach())["sample"]
         if return_type == "np":
-            image = (image / 2 + 0.5).clamp(0, 1).cpu().permute(0, 2, 3, 1).numpy()[0]
-            image = (image * 255).astype("uint8")
+            from . import ptp_utils
+            image = ptp_utils.image_to_uint8(image)[0]
         return image
 
     @torch.no_grad()
@@ -272,10 +272,10 @@ class NullInversion:
         vae = getattr(self.model, "vae", None)
         if vae is None:
             raise ValueError("this pipeline has no VAE: pass the image latent [1, 4, H/8, W/8]")
-        import numpy as np
-        x = torch.from_numpy(np.asarray(image)).float() / 127.5 - 1
-        x = x.permute(2, 0, 1).unsqueeze(0).to(self.model.device)
-        return vae.encode(x)["latent_dist"].mean * 0.18215
+        from . import ptp_utils
+        x = ptp_utils.image_to_model(image, self.model.device, vae.dtype)
+        # (f32, as every latent of this pipeline, whatever the VAE's dtype)
+        return (vae.encode(x)["latent_dist"].mean * 0.18215).float()
 
     @torch.no_grad()
     def init_prompt(self, prompt: str):

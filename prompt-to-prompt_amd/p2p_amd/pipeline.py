@@ -37,9 +37,14 @@ class SyntheticTextEncoder(nn.Module):
 class SyntheticStableDiffusion:
     """``scheduler``: "ddim" (null_text.py:16-20) or "pndm" (the PLMS sampler the v1.4 pipeline of
     main.py:29 carries: skip_prk_steps, steps_offset 1).  ``unet_config``: keyword arguments of the
-    U-Net in place of the SD-v1.4 shape (tests run a narrow one)."""
+    U-Net in place of the SD-v1.4 shape (tests run a narrow one).  ``vae``: also build the
+    random-init SD-shaped ``vae.AutoencoderKL`` (or, with ``vae_config``, one of those keyword
+    arguments) in the U-Net's dtype, so that text2image_ldm_stable returns images and NullInversion
+    takes one; the default has none and works on latents.  It is built last: the seeded weights of
+    everything else are the same with and without it."""
 
-    def __init__(self, device="cuda", dtype=torch.float32, seed=0, scheduler="ddim", unet_config=None):
+    def __init__(self, device="cuda", dtype=torch.float32, seed=0, scheduler="ddim", unet_config=None,
+                 vae=False, vae_config=None):
         self.device = torch.device(device)
         self.tokenizer = default_tokenizer()
         torch.manual_seed(seed)
@@ -56,6 +61,11 @@ class SyntheticStableDiffusion:
         else:
             raise ValueError(f"scheduler {scheduler!r}: 'ddim' or 'pndm'")
         self.vae = None
+        if vae or vae_config is not None:
+            from .vae import AutoencoderKL
+            self.vae = AutoencoderKL(**(vae_config or {})).to(self.device, dtype).eval()
+            for p in self.vae.parameters():
+                p.requires_grad_(False)
 
 
 class SyntheticLatentDiffusion:

@@ -106,13 +106,41 @@ def _blend_launch_ok(x, out, eps, folded, more=()) -> bool:
     return (H * W) % 4 == 0 and res <= H and res <= W and res * res <= 256 and ptrs % 16 == 0
 
 
-def latent2image(vae, latents):
-    """ptp_utils.py:79-85 (needs a VAE; the synthetic pipeline has none)."""
-    latents = 1 / 0.18215 * latents
-    image = vae.decode(latents)["sample"]
-    image = (image / 2 + 0.5).clamp(0, 1)
+def image_to_uint8(image: torch.Tensor) -> np.ndarray:
+    """A decoder output [N, 3, H, W] (any float dtype) as the reference's uint8 ndarray [N, H, W, 3]
+    (ptp_utils.py:82-85).  On the GPU one kernel (p2p_image_u8, the same bytes); the torch lines
+    serve the CPU and the sizes the kernel does not take."""
+    if image.is_cuda:
+        from . import _hip
+        out = _hip.image_u8(image.contiguous())
+        if out is not None:
+            return out.cpu().numpy()
+    image = (image.float() / 2 + 0.5).clamp(0, 1)   # (.float(): numpy has no bfloat16)
     image = image.cpu().permute(0, 2, 3, 1).numpy()
     return (image * 255).astype(np.uint8)
+
+
+def image_to_model(image, device, dtype) -> torch.Tensor:
+    """uint8 pixels [H, W, 3] (or [N, H, W, 3]) as the VAE encoder's input [N, 3, H, W] in ``dtype``:
+    x / 127.5 - 1 (null_text.py:523-525), on the GPU by p2p_image_to_model."""
+    x = torch.from_numpy(np.ascontiguousarray(np.asarray(image)))
+    if x.dim() == 3:
+        x = x[None]
+    device = torch.device(device)
+    if device.type == "cuda" and x.dtype == torch.uint8:
+        from . import _hip
+        out = _hip.image_to_model(x.to(device), dtype)
+        if out is not None:
+            return out
+    x = x.float() / 127.5 - 1
+    return x.permute(0, 3, 1, 2).contiguous().to(device, dtype)   # dense NCHW, as the kernel writes it
+
+
+def latent2image(vae, latents):
+    """ptp_utils.py:79-85: decode, then uint8 [N, H, W, 3]."""
+    latents = 1 / 0.18215 * latents
+    image = vae.decode(latents)["sample"]
+    return image_to_uint8(image)
 
 
 def init_latent(latent, model, height, width, generator, batch_size):
@@ -167,8 +195,9 @@ def text2image_ldm_stable(model, prompt: List[str], controller, num_inference_st
                           latent: Optional[torch.FloatTensor] = None, low_resource: bool = False,
                           uncond_embeddings=None):
     """ptp_utils.py:129-172.  ``uncond_embeddings`` (per-step list or one tensor) is the
-    argument the missing null-text notebook passes for the edit after inversion.  Without a
-    VAE on the model the final latents are returned in place of the image."""
+    argument the missing null-text notebook passes for the edit after inversion.  With a VAE on
+    the model (SyntheticStableDiffusion(vae=True)) the images come back as the reference returns
+    them, uint8 [N, 512, 512, 3]; without one, the final latents in their place."""
     register_attention_control(model, controller)
     height = width = 512
     batch_size = len(prompt)

@@ -158,7 +158,9 @@ class ResnetBlock2D(nn.Module):
         super().__init__()
         self.norm1 = nn.GroupNorm(groups, in_ch, eps=eps)
         self.conv1 = nn.Conv2d(in_ch, out_ch, 3, padding=1)
-        self.time_emb_proj = nn.Linear(temb_ch, out_ch)
+        # temb_ch None: the VAE's resnets (vae.py), which take no time embedding and have no projection
+        if temb_ch is not None:
+            self.time_emb_proj = nn.Linear(temb_ch, out_ch)
         self.norm2 = nn.GroupNorm(groups, out_ch, eps=eps)
         self.conv2 = nn.Conv2d(out_ch, out_ch, 3, padding=1)
         self.conv_shortcut = nn.Conv2d(in_ch, out_ch, 1) if in_ch != out_ch else None
@@ -171,7 +173,8 @@ class ResnetBlock2D(nn.Module):
         if h is None:
             return None
         h = c1._conv_forward(h, c1.weight, None)
-        h = _norm_act(self.norm2, h, silu=True, chan_add=self.time_emb_proj(F.silu(temb)), chan_bias=c1.bias)
+        chan_add = self.time_emb_proj(F.silu(temb)) if temb is not None else None
+        h = _norm_act(self.norm2, h, silu=True, chan_add=chan_add, chan_bias=c1.bias)
         if h is None:
             return None
         h = c2._conv_forward(h, c2.weight, None)
@@ -179,13 +182,14 @@ class ResnetBlock2D(nn.Module):
             return _hip.bias_residual(sc._conv_forward(x, sc.weight, None), h, c2.bias, sc.bias)
         return _hip.bias_residual(x, h, c2.bias)
 
-    def forward(self, x, temb):
-        if fused_glue(x, temb, self.conv1.weight):
+    def forward(self, x, temb=None):
+        if fused_glue(x, self.conv1.weight, *(() if temb is None else (temb,))):
             out = self._forward_fused(x, temb)
             if out is not None:
                 return out
         h = self.conv1(F.silu(self.norm1(x)))
-        h = h + self.time_emb_proj(F.silu(temb))[:, :, None, None]
+        if temb is not None:
+            h = h + self.time_emb_proj(F.silu(temb))[:, :, None, None]
         h = self.conv2(F.silu(self.norm2(h)))
         if self.conv_shortcut is not None:
             x = self.conv_shortcut(x)
