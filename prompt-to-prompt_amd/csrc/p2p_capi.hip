@@ -50,9 +50,10 @@ void fill_common(A& a, const p2p_attn_tensors* t) {
   no_maps(a);
 }
 
-// Kernel variants for A/B timing (tools/self_variants.py): honoured only by a library built with
-// `make EXPERIMENTS=1`, and read once at load -- a production library always runs the default
-// kernels whatever the environment says.
+// P2P_SELF_VARIANT, the clock-stamp diagnostics of p2p_select.h's Variant: honoured only by a
+// library built with `make EXPERIMENTS=1`, and read once at load (setting it later in the process
+// changes nothing; a value that is no Variant makes every attention call return P2P_E_ARG) -- a
+// production library always runs the default kernels whatever the environment says.
 #ifdef P2P_EXPERIMENTS
 const int kSelfVariant = [] {
   const char* e = getenv("P2P_SELF_VARIANT");

@@ -30,11 +30,11 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 
 #ifdef P2P_EXPERIMENTS
-// diagnostic clock stamps (experiments build, P2P_SELF_VARIANT 123): [logical workgroup < 2048]
+// diagnostic clock stamps (experiments build, VARIANT_GROUP_STAMPS): [logical workgroup < 2048]
 // [wave < 4][slot < 24]; read back by p2p_diag_group_stamps (tools/group_stamps.py)
 __device__ unsigned long long g_group_stamps[2048 * 4 * 24];
 #define P2P_GROUP_STAMP(i)                                                                         \
-  if (a.variant == 123 && logical < 2048 && wave < 4 && lane == 0 && (i) < 24)                     \
+  if (a.variant == VARIANT_GROUP_STAMPS && logical < 2048 && wave < 4 && lane == 0 && (i) < 24)    \
     g_group_stamps[(logical * 4 + wave) * 24 + (i)] = __builtin_amdgcn_s_memtime();
 #else
 #define P2P_GROUP_STAMP(i) do { } while (0);
@@ -654,7 +654,8 @@ hipError_t launch_group(const CrossArgs& a, CrossKernel k, hipStream_t st) {
 }  // namespace
 
 // bf16 inputs and compute, no term-plane (non-dense) programs: which launches come here is
-// p2p_select.h's.  (The d = 80 / 160 instantiations remain in the experiments build, variant 123.)
+// p2p_select.h's.  (The d = 80 / 160 instantiations remain in the experiments build,
+// VARIANT_GROUP_STAMPS.)
 int launch_cross_group(const CrossArgs& a, int d, CrossKernel k, hipStream_t st) {
   if (!is_group(k)) return P2P_E_ARG;
   switch (d) {

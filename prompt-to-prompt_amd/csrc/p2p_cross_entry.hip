@@ -26,11 +26,11 @@ namespace p2p {
 // wave).  The slab is dynamic LDS, allocated only by launches with an edit or a store, so a
 // plain launch runs at the occupancy of its K/V tiles alone.
 #ifdef P2P_EXPERIMENTS
-// diagnostic clock stamps of the cross kernel (experiments build, P2P_SELF_VARIANT 90):
+// diagnostic clock stamps of the cross kernel (experiments build, VARIANT_CROSS_STAMPS):
 // [logical workgroup < 4096][wave < 4][slot < 24]; read back by p2p_diag_cross_stamps
 __device__ unsigned long long g_cross_stamps[4096 * 4 * 24];
 #define P2P_CROSS_STAMP(i)                                                                              \
-  if (a.variant == 90 && logical < 4096 && wave < 4 && lane == 0)                                       \
+  if (a.variant == VARIANT_CROSS_STAMPS && logical < 4096 && wave < 4 && lane == 0)                     \
     g_cross_stamps[(logical * 4 + wave) * 24 + (i)] = __builtin_amdgcn_s_memtime();
 #else
 #define P2P_CROSS_STAMP(i) do { } while (0);

@@ -46,7 +46,7 @@ struct SelfArgs {
   const float* probs;          // MODE_PV input [N*H, P, K]
   const uint8_t* key_mask;     // optional [N, K]
   int store_accumulate;
-  int variant;                 // fused-kernel tile shape (P2P_SELF_VARIANT, timing experiments)
+  int variant;                 // a Variant of p2p_select.h (P2P_SELF_VARIANT, experiments build only), else 0
   float* lse;                  // optional [N*H, P] row log-sum-exp output (fused mode, autograd)
   int qk_src[P2P_MAX_BATCH];
   int store_slot[P2P_MAX_BATCH];
@@ -72,7 +72,7 @@ struct CrossArgs {
   int edit_dense;                // some group carries the dense f16 mapper tile
   int slab;                      // launcher-filled: the launch allocates the LDS slab
   int slab_stride;               // launcher-filled
-  int variant;                   // launch-shape experiments (P2P_SELF_VARIANT, experiments build only)
+  int variant;                   // a Variant of p2p_select.h (P2P_SELF_VARIANT, experiments build only), else 0
   int store_slot[P2P_MAX_BATCH];
   int ent_group[P2P_MAX_BATCH];  // prompt group of every batch entry
   // per entry, packed so ONE kernel-argument load after n decides the path: group (bits 0-7),

@@ -13,6 +13,20 @@ namespace p2p {
 
 enum { MODE_FUSED_ = 0, MODE_PV_ = 3 };
 
+// P2P_SELF_VARIANT: the values an experiments build honours, each a clock-stamp diagnostic of one
+// kernel (read once at load; select_self / select_cross refuse any other non-zero value with
+// P2P_E_ARG).  A production build compiles the variable out and always passes 0.
+enum Variant {
+  VARIANT_CROSS_STAMPS = 90,    // cross_attn_kernel (tools/cross_stamps.py)
+  VARIANT_GROUP_STAMPS = 123,   // cross_group_kernel, at d = 80 / 160 too (tools/group_stamps.py)
+  VARIANT_SELF40_STAMPS = 163,  // self40_kernel at d = 40 (tools/s40_stamps.py)
+  VARIANT_SELF80_STAMPS = 164,  // self40_kernel at d = 80
+};
+inline bool variant_known(int v) {
+  return v == 0 || v == VARIANT_CROSS_STAMPS || v == VARIANT_GROUP_STAMPS || v == VARIANT_SELF40_STAMPS ||
+         v == VARIANT_SELF80_STAMPS;
+}
+
 // ---------------------------------------------------------------------------- precision, head dim
 // (io_dtype, compute) -> the (IO, MQ, MP) triple of the kernels: exact-f32 check mode; the bf16
 // pipe on f32 inputs (split-bf16 QK^T so the logits keep f32 grade, bf16 PV); bf16 inputs (one
@@ -53,8 +67,8 @@ enum SelfForm { FORM_DEFAULT, FORM_EXACT, FORM_NOMAX };
 // triple and D for the head dim, both inputs of the selection -- so a name (and a test that asserts
 // it) tells the kernel family, tile shape and form, not which precision's or head dim's
 // instantiation the launcher then takes; that step is with_precision / with_head_dim
-// (p2p_device.h), one switch each, covered by the numeric tests.  The split 3x2 / 4x2 shapes and the
-// experiments forms are compiled but never selected by a production build.
+// (p2p_device.h), one switch each, covered by the numeric tests.  Every row is a kernel some build
+// can select; the STAMPS rows are compiled and selected by the experiments build only.
 #define P2P_SELF_KERNELS(X)                                                                              \
   X(SELF_FUSED_32x2, FAM_FUSED, 32, 2, FORM_DEFAULT, "self_attn_fused_kernel<…,D,32,2>")                 \
   X(SELF_FUSED_32x2_EXACT, FAM_FUSED, 32, 2, FORM_EXACT, "self_attn_fused_kernel<…,D,32,2,EXACT>")       \
@@ -75,7 +89,6 @@ enum SelfForm { FORM_DEFAULT, FORM_EXACT, FORM_NOMAX };
   X(SELF_MULTI_128, FAM_MULTI, 128, 8, FORM_NOMAX, "self_attn_multi_kernel<…,40,128,8,2>")               \
   X(SELF40_D40, FAM_SELF40, 256, 8, FORM_NOMAX, "self40_kernel<40,8,2,256>")                             \
   X(SELF40_D40_H16, FAM_SELF40, 256, 8, FORM_NOMAX, "self40_kernel<40,8,2,256,H16>")                     \
-  X(SELF40_D40_ROUND3, FAM_SELF40, 256, 8, FORM_NOMAX, "self40_kernel<40,8,2,256,FORM=17281>")           \
   X(SELF40_D40_STAMPS, FAM_SELF40, 256, 8, FORM_NOMAX, "self40_kernel<40,8,2,256,STAMPS>")               \
   X(SELF40_D80, FAM_SELF40, 128, 8, FORM_NOMAX, "self40_kernel<80,8,1,128>")                             \
   X(SELF40_D80_H16, FAM_SELF40, 128, 8, FORM_NOMAX, "self40_kernel<80,8,1,128,H16>")                     \
@@ -83,8 +96,6 @@ enum SelfForm { FORM_DEFAULT, FORM_EXACT, FORM_NOMAX };
   X(SELF_SPLIT_1x1, FAM_SPLIT, 1, 1, FORM_DEFAULT, "self_split_kernel<160,1,1>")                         \
   X(SELF_SPLIT_2x1, FAM_SPLIT, 1, 2, FORM_DEFAULT, "self_split_kernel<160,2,1>")                         \
   X(SELF_SPLIT_2x2, FAM_SPLIT, 2, 2, FORM_DEFAULT, "self_split_kernel<160,2,2>")                         \
-  X(SELF_SPLIT_3x2, FAM_SPLIT, 2, 3, FORM_DEFAULT, "self_split_kernel<160,3,2>")                         \
-  X(SELF_SPLIT_4x2, FAM_SPLIT, 2, 4, FORM_DEFAULT, "self_split_kernel<160,4,2>")                         \
   X(SELF_HALVES, FAM_HALVES, 32, 4, FORM_DEFAULT, "self_halves_kernel")                                  \
   X(SELF_RING, FAM_RING, 32, 4, FORM_DEFAULT, "self_ring_kernel<160,4>")                                 \
   X(SELF_WIDE, FAM_WIDE, 64, 4, FORM_DEFAULT, "self_wide_kernel<512,…>")
@@ -149,9 +160,14 @@ inline SelfKernel select_fused(int prec, int d, int P, bool lse, bool maps) {
 
 // The kernel a self launch runs, or a negative P2P_E_* code.  mode: MODE_FUSED_ (O, and the lse when
 // `lse` or `maps`) or MODE_PV_ (the materialise protocol's P V).  variant: P2P_SELF_VARIANT of the
-// experiments build (A/B timing tools), 0 in production.
+// experiments build (a Variant or 0; anything else: P2P_E_ARG), 0 in production.
 inline int select_self(int io_dtype, int compute, int d, int P, int K, int mode, bool lse, bool maps,
                        int variant) {
+#ifdef P2P_EXPERIMENTS
+  if (!variant_known(variant)) return P2P_E_ARG;
+#else
+  (void)variant;
+#endif
   const int prec = select_precision(io_dtype, compute);
   if (prec < 0) return prec;
   // d = 512 (the VAE's mid-block attention, one head as wide as the layer): p2p_selfwide.hip, the
@@ -161,7 +177,6 @@ inline int select_self(int io_dtype, int compute, int d, int P, int K, int mode,
   if (d == kWideHeadDim && mode == MODE_FUSED_ && !lse && !maps && (prec == PREC_BF16 || prec == PREC_F16))
     return SELF_WIDE;
   if (!head_dim_compiled(d)) return P2P_E_HEAD_DIM;
-  (void)variant;
   if (mode == MODE_PV_) return fused_bk(d, prec != PREC_F32) == 32 ? SELF_PV_32x4 : SELF_PV_64x4;
   lse = lse || maps;
   const bool o_only = !lse;   // nothing but O wanted: no kept maps, no autograd
@@ -174,8 +189,7 @@ inline int select_self(int io_dtype, int compute, int d, int P, int K, int mode,
     if (d == 40 && P >= 2048) {
       if (h16) return SELF40_D40_H16;
 #ifdef P2P_EXPERIMENTS
-      if (variant == 163) return SELF40_D40_STAMPS;   // default with clock stamps
-      if (variant == 17281) return SELF40_D40_ROUND3; // round-3 default
+      if (variant == VARIANT_SELF40_STAMPS) return SELF40_D40_STAMPS;   // default with clock stamps
 #endif
       // LEAN fragments, split staging (waves 0-3 K, 4-7 V), the younger half holding priority 1 on
       // three of every four steps (round 3: 0.1867 ms vs 0.1880-0.1885 for priority on alternate
@@ -187,7 +201,7 @@ inline int select_self(int io_dtype, int compute, int d, int P, int K, int mode,
     if (d == 80 && P >= 512) {
       if (h16) return SELF40_D80_H16;
 #ifdef P2P_EXPERIMENTS
-      if (variant == 164) return SELF40_D80_STAMPS;   // default + stamps
+      if (variant == VARIANT_SELF80_STAMPS) return SELF40_D80_STAMPS;   // default with clock stamps
 #endif
       // d = 80: 8 waves x ONE 32-row query block (two waves per SIMD), 128-key tiles, split staging
       // and the younger half's priority duty of the d = 40 kernel.  In the pipeline (bench.py,
@@ -263,11 +277,15 @@ constexpr int cross_waves(int d, bool mp16) { return (!mp16 && d >= 128) ? 2 : 4
 // its maps.
 inline int select_cross(int io_dtype, int compute, int d, int n_groups, int H, int P, int K, bool edit_terms,
                         bool edit_dense, bool any_store, int variant) {
+#ifdef P2P_EXPERIMENTS
+  if (!variant_known(variant)) return P2P_E_ARG;
+#else
+  (void)variant;
+#endif
   const int prec = select_precision(io_dtype, compute);
   if (prec < 0) return prec;
   if (K > P2P_MAX_KEYS_CROSS) return P2P_E_KEYS;
   if (!head_dim_compiled(d)) return P2P_E_HEAD_DIM;
-  (void)variant;
   // The group-coupled kernel (p2p_cross.hip): bf16 inputs and compute, no term-plane (non-dense)
   // programs (fp16 takes the per-entry kernel).
   // The workgroup walks the group's entries one after another, so it only pays where the grid
@@ -277,12 +295,12 @@ inline int select_cross(int io_dtype, int compute, int d, int n_groups, int H, i
   // G2/G6) the group kernel -- four entries with their map stores walked in sequence -- measured
   // 228.5 us per launch against the per-entry kernel's 131.4 (profiles/r04/group_vs_entry_r04aj/);
   // at d = 40 it stays ahead (146.9 vs 215.0 us).  (The d = 80 / 160 instantiations remain in the
-  // experiments build, variant 123.)
+  // experiments build, VARIANT_GROUP_STAMPS.)
   if (prec == PREC_BF16 && !edit_terms) {
     const int wgs = n_groups * H * ((P + 127) / 128);
     bool group = d == 40 && wgs >= 512;
 #ifdef P2P_EXPERIMENTS
-    if (variant == 123) group = d == 40 || d == 80 || d == 160;   // clock stamps (tools/group_stamps.py)
+    if (variant == VARIANT_GROUP_STAMPS) group = d == 40 || d == 80 || d == 160;   // (tools/group_stamps.py)
 #endif
     if (group) return CROSS_GROUP + (edit_dense ? 2 : 0) + (any_store ? 1 : 0);
   }

@@ -7,9 +7,9 @@
 // so every MFMA has exponentials of an independent block beside it and every exponential an
 // MFMA: the wave's own instruction stream interleaves the matrix pipe and the VALU instead of
 // relying on a co-resident wave to fill the gaps (MI355X_MICROARCH.md, "one wave per SIMD").
-// K/V fragments for sub-block sb+1 are read from LDS while sub-block sb computes (double-
-// buffered fragments), and the next tile's K/V are staged into the other LDS buffer by
-// register staging spread over the second half of the tile.
+// A wave holds one K and one V fragment set, each re-read from LDS right after its last reader,
+// and the next tile's K/V are staged into the other LDS buffer by register staging spread over
+// the second half of the tile.
 //
 // Arithmetic (the F16 form of round 2, kept): Q is prescaled by c = scale*log2(e) and rounded
 // to f16; K is staged as f16 (exact for bf16 values in range); d pads to 48 and the padding
@@ -87,7 +87,7 @@ __device__ __forceinline__ void mma_bf16(f32x16_t& acc, const short8_t& a, const
 }
 
 #ifdef P2P_EXPERIMENTS
-// Diagnostic build (FORM bit 16, experiments library only): per-wave shader-clock stamps of the
+// Diagnostic build (STAMPS, experiments library only): per-wave shader-clock stamps of the
 // first 256 workgroups, read back by p2p_diag_self40_stamps (tools/s40_stamps.py).
 // slots 38 / 39: s_memrealtime (100 MHz, one clock for every XCD) at the start / end, for the
 // launch's workgroup timeline; stamps of the first 1024 workgroups
@@ -99,13 +99,24 @@ __device__ unsigned long long g_s40_stamps[kStampWgs * 8 * kStampSlots];
 // One workgroup = WAVES waves x QB query blocks of 32 rows = 32*QB*WAVES queries of one (entry,
 // head); BK-key tiles, double-buffered in LDS.
 //
-// FORM bits (measured-and-dropped variants live in git history, DESIGN.md §4 cites their logs):
-//   1        LEAN fragment buffering (one K and one V fragment set per wave)
-//   16       clock stamps (experiments build only)
-//   128      split staging: waves 0..WAVES/2-1 stage K (the f16 conversion), the rest V
-//   256/512/16384  the younger half holds priority 1 for 3 of every 4 steps
-//   8388608  K's f16 range check as a packed-u16 maximum
-template <int kD, int WAVES, int QB, int BK, bool SCHED, int FORM, bool H16 = false>
+// The one form, each feature chosen by measurement (the alternatives -- every wave staging both K
+// and V, double-buffered fragment sets, other priority duties, an f32 maximum for K's range check,
+// no scheduling barriers -- are in git history before this form; DESIGN.md §4 cites their logs):
+//   - lean fragments: one K and one V fragment set per wave, each re-read from LDS right after
+//     its last reader (profiles/r03/g1_ab/r03y_ab.log);
+//   - split staging: waves 0..WAVES/2-1 stage K (the f16 conversion), the younger half -- the
+//     VALU-arbitration loser -- stages V, a plain copy (profiles/r03/g1_ab/r03y_ab.log; d = 80:
+//     profiles/r05/d80_ab/);
+//   - the younger half holds priority 1 for 3 of every 4 steps, so the two waves of a SIMD share
+//     the VALU evenly (0.1867 ms against 0.1880-0.1885 for alternate step pairs,
+//     profiles/r03/g1_ab/r03y_ab.log);
+//   - bf16 K's f16 range check is a packed-u16 maximum of the magnitudes, compared once at the end
+//     (0.1864-0.1865 against 0.1881-0.1889 ms for an f32 maximum per chunk,
+//     profiles/r04/ab/g1_r04h.log);
+//   - sched_group_barriers pin one MFMA per slot with the step's exponentials and VALU spread
+//     over the slots.
+// STAMPS (experiments build only): the clock stamps above.
+template <int kD, int WAVES, int QB, int BK, bool H16 = false, bool STAMPS = false>
 __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(SelfArgs a) {
   using G = Geom<kD>;
   constexpr bool kF16 = G::F16;
@@ -123,22 +134,18 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
   static_assert(((kLrr >> 2) & 1) == 0, "the row sum sits in the low lane half");
   constexpr int NSB = BK / 32;
   constexpr int NT = 64 * WAVES;
-  constexpr int NCH = (BK * kCPR + NT - 1) / NT;
   constexpr int KBUF = BK * kKS;
   constexpr int VBUF = BK * kVS;
   constexpr int X = NSB * QB;   // pipeline steps (32x32 blocks) per tile
   constexpr float kThr = 8.0f;  // exact path: defer-max threshold (log2 units)
-  // FORM bit 128 (split staging): waves 0..WAVES/2-1 stage K (the f16 conversion), the younger
-  // half -- the VALU-arbitration loser -- stages V (copy only); else every wave stages both
-  constexpr bool kSplit = (FORM & 128) != 0;
-  constexpr int SCH = (BK * kCPR + NT / 2 - 1) / (NT / 2);   // chunks per thread, split staging
-  constexpr int CMAX = kSplit ? SCH : NCH;
+  // split staging: waves 0..WAVES/2-1 stage K (the f16 conversion), the younger half V (copy
+  // only), so a thread holds SCH 16-byte chunks of a tile
+  constexpr int SCH = (BK * kCPR + NT / 2 - 1) / (NT / 2);
   // staging writes: chunk i of the next tile at step kWs + i (X - kWs) / n (several per step
   // when there are more chunks than steps), from the middle of the tile on -- the loads issued at
   // its start have landed by then
   constexpr int kWs = X / 2;
   constexpr int kWe = X;
-  auto nchunks = [](auto role) { return decltype(role)::value == 0 ? NCH : SCH; };
   // K and V tile buffers; after the last tile the same LDS holds each wave's output rows (epilogue)
   __shared__ __attribute__((aligned(16))) uint16_t smem[2 * KBUF + 2 * VBUF];
   uint16_t* const Ks = smem;
@@ -162,7 +169,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
   const int logical = xcd_remap(blockIdx.x, gridDim.x);
   auto stamp = [&](int idx) __attribute__((always_inline)) {
 #ifdef P2P_EXPERIMENTS
-    if constexpr ((FORM & 16) != 0)
+    if constexpr (STAMPS)
       if (logical < kStampWgs && lane == 0 && idx < kStampSlots) {
         g_s40_stamps[(logical * WAVES + wave) * kStampSlots + idx] = __builtin_amdgcn_s_memtime();
         if (idx == 0 || idx == 37)
@@ -203,11 +210,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
 
   // ---- Q fragments: lane (qi, hh) of block b, k step t holds Q[p][16t + 8hh .. +7]
   bool ovf = false;
-  // FORM bit 8388608: K's f16 range check as a running packed u16 maximum of the bf16 magnitudes
-  // (v_and + v_pk_max_u16 per pair), compared once at the end: a bf16 magnitude >= 0x4780 (65536,
-  // past the f16 range; inf / NaN included) sends the workgroup to the exact path -- instead of an
-  // f32 |x| maximum per chunk (the fmaxf NaN canonicalisation made that ~3.5 VALU per pair)
-  constexpr bool kU16Max = (FORM & 8388608) != 0;
+  // bf16 inputs in the F16 form (d = 40): K is converted to f16 on its way into LDS, and its f16
+  // range check is a running packed u16 maximum of the bf16 magnitudes (v_and + v_pk_max_u16 per
+  // pair), compared once at the end: a bf16 magnitude >= 0x4780 (65536, past the f16 range; inf /
+  // NaN included) sends the workgroup to the exact path.  fp16 inputs and d = 80 never convert.
+  constexpr bool kCvtK = kF16 && !H16;
   typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
   typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
   u16x2_t kmag = {0, 0};
@@ -245,60 +252,52 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
       if (hh == (kD % 16) / 8) qf[b][kD / 16][kD % 8] = (short)__builtin_bit_cast(uint16_t, (_Float16)(-m));
   };
 
-  // ---- K/V staging: chunk i of this thread = row cidx / 5, 16-byte chunk cidx % 5 (role 0: both
-  // K and V of the chunk; split staging: role 1 = K chunks of threads 0..NT/2-1, role 2 = V
-  // chunks of the others, each thread holding SCH of them in kreg)
+  // ---- K/V staging: chunk i of this thread = row cidx / 5, 16-byte chunk cidx % 5 of the K tile
+  // (threads 0..NT/2-1) or of the V tile (the others, the younger half: vrole), each thread holding
+  // SCH of them in kreg.  The lambdas take the role as a compile-time bool (true: V).
   const bool young = __builtin_amdgcn_readfirstlane(wave) >= WAVES / 2;
   const bool vrole = young;
-  const int stid = kSplit ? tid - (young ? NT / 2 : 0) : tid;   // (position within the half)
-  const int sstride = kSplit ? NT / 2 : NT;
-  short8_t kreg[CMAX], vreg[NCH];
-  uint32_t koff[CMAX], voff[NCH];
-  int lrow[CMAX], lch[CMAX];
+  const int stid = tid - (young ? NT / 2 : 0);   // (position within the half)
+  short8_t kreg[SCH];
+  uint32_t koff[SCH];
+  int lrow[SCH], lch[SCH];
 #pragma unroll
-  for (int i = 0; i < CMAX; ++i) {
-    const int cidx = stid + i * sstride;
+  for (int i = 0; i < SCH; ++i) {
+    const int cidx = stid + i * (NT / 2);
     const int row = min(cidx / kCPR, BK - 1);
     const int ch = cidx - (cidx / kCPR) * kCPR;
     lrow[i] = row;
     lch[i] = ch;
-    koff[i] = (uint32_t)((row * (int)(kSplit && vrole ? a.ldv : a.ldk) + ch * 8) * 2);
-    if (i < NCH) voff[i] = (uint32_t)((row * (int)a.ldv + ch * 8) * 2);
+    koff[i] = (uint32_t)((row * (int)(vrole ? a.ldv : a.ldk) + ch * 8) * 2);
   }
   const int64_t kbytes = ((int64_t)(K - 1) * a.ldk + kD) * 2;
   const int64_t vbytes = ((int64_t)(K - 1) * a.ldv + kD) * 2;
   const int64_t kstep = (int64_t)BK * a.ldk * 2;
   const int64_t vstep = (int64_t)BK * a.ldv * 2;
-  auto chunk_live = [&](int i, auto role) __attribute__((always_inline)) {
-    constexpr int sn = decltype(role)::value == 0 ? NT : NT / 2;
-    return (BK * kCPR) % sn == 0 || stid + i * sn < BK * kCPR;
+  auto chunk_live = [&](int i) __attribute__((always_inline)) {
+    return (BK * kCPR) % (NT / 2) == 0 || stid + i * (NT / 2) < BK * kCPR;
   };
-  auto stage_load = [&](int kt, auto role) __attribute__((always_inline)) {
-    constexpr int kRole = decltype(role)::value;
+  auto stage_load = [&](int kt, auto vr) __attribute__((always_inline)) {
     const __amdgpu_buffer_rsrc_t rk = make_rsrc(reinterpret_cast<const char*>(kp) + kt * kstep, kbytes - kt * kstep);
     const __amdgpu_buffer_rsrc_t rv = make_rsrc(reinterpret_cast<const char*>(vp) + kt * vstep, vbytes - kt * vstep);
 #pragma unroll
-    for (int i = 0; i < nchunks(role); ++i)
-      if (chunk_live(i, role)) {
-        kreg[i] = __builtin_bit_cast(short8_t, __builtin_amdgcn_raw_buffer_load_b128(kRole == 2 ? rv : rk, (int)koff[i], 0, 0));
-        if constexpr (kRole == 0)
-          vreg[i] = __builtin_bit_cast(short8_t, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)voff[i], 0, 0));
-      }
+    for (int i = 0; i < SCH; ++i)
+      if (chunk_live(i))
+        kreg[i] = __builtin_bit_cast(short8_t, __builtin_amdgcn_raw_buffer_load_b128(decltype(vr)::value ? rv : rk, (int)koff[i], 0, 0));
   };
-  // chunk i into LDS buffer buf: K as f16 (fast form; exact for magnitudes in [2^-14, 65504] --
-  // smaller ones become f16 subnormals, absolute error < 2^-25 --, RTZ packing would clamp past
-  // 65504 silently, so the range is checked) or raw bf16 (exact path)
-  auto stage_write = [&](int i, int buf, bool as_f16, auto role) __attribute__((always_inline)) {
-    constexpr int kRole = decltype(role)::value;
-    if (!chunk_live(i, role)) return;
-    if constexpr (kRole == 2) {
+  // chunk i into LDS buffer buf: V as it is; K as f16 (fast form; exact for magnitudes in [2^-14,
+  // 65504] -- smaller ones become f16 subnormals, absolute error < 2^-25 --, RTZ packing would
+  // clamp past 65504 silently, so the range is checked) or raw bf16 (exact path)
+  auto stage_write = [&](int i, int buf, bool as_f16, auto vr) __attribute__((always_inline)) {
+    if (!chunk_live(i)) return;
+    if constexpr (decltype(vr)::value) {
       *reinterpret_cast<short8_t*>(Vs + buf * VBUF + lrow[i] * kVS + lch[i] * 8) = kreg[i];
       return;
     }
     uint16_t* const kd = Ks + buf * KBUF + lrow[i] * kKS + lch[i] * 8;
-    if (H16 || !as_f16) {   // raw bf16 (exact path), or fp16 inputs: K is f16 already
+    if (H16 || !as_f16) {   // raw bf16 (d = 80, exact path), or fp16 inputs: K is f16 already
       *reinterpret_cast<short8_t*>(kd) = kreg[i];
-    } else if (kU16Max) {
+    } else {
       const u32x4_t wv = __builtin_bit_cast(u32x4_t, kreg[i]);
       u32x4_t hv;
 #pragma unroll
@@ -309,32 +308,17 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
                                                                        __uint_as_float(w & 0xffff0000u)));
       }
       *reinterpret_cast<u32x4_t*>(kd) = hv;
-    } else {
-      short8_t hv;
-      float mx = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        const float x0 = bf2f((uint16_t)kreg[i][j]), x1 = bf2f((uint16_t)kreg[i][j + 1]);
-        mx = fmaxf(mx, fmaxf(fabsf(x0), fabsf(x1)));
-        const auto pk = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-        hv[j] = (short)(pk & 0xffff);
-        hv[j + 1] = (short)(pk >> 16);
-      }
-      ovf |= !(mx < 65504.f);
-      *reinterpret_cast<short8_t*>(kd) = hv;
     }
-    if constexpr (kRole == 0) *reinterpret_cast<short8_t*>(Vs + buf * VBUF + lrow[i] * kVS + lch[i] * 8) = vreg[i];
   };
-  // a whole tile into buf, for the role(s) of this wave (prologue and exact recompute)
+  // a whole tile into buf, for the role of this wave (prologue and exact recompute)
   auto stage_all = [&](int kt, int buf, bool as_f16) __attribute__((always_inline)) {
-    auto go = [&](auto role) __attribute__((always_inline)) {
-      stage_load(kt, role);
+    auto go = [&](auto vr) __attribute__((always_inline)) {
+      stage_load(kt, vr);
 #pragma unroll
-      for (int i = 0; i < nchunks(role); ++i) stage_write(i, buf, as_f16, role);
+      for (int i = 0; i < SCH; ++i) stage_write(i, buf, as_f16, vr);
     };
-    if constexpr (!kSplit) go(std::integral_constant<int, 0>{});
-    else if (vrole) go(std::integral_constant<int, 2>{});
-    else go(std::integral_constant<int, 1>{});
+    if (vrole) go(std::true_type{});
+    else go(std::false_type{});
   };
 
   const int ntiles = (K + BK - 1) / BK;
@@ -390,43 +374,38 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
   // ---- one tile of the fast form, software-pipelined over its X blocks.  more: the next tile
   // is staged during this one (compile-time, so the tile body is one basic block); masked: keys
   // past K in this tile
-  auto tile = [&](int kt, auto more, auto masked, auto role) __attribute__((always_inline)) {
+  auto tile = [&](int kt, auto more, auto masked, auto vr) __attribute__((always_inline)) {
     constexpr bool kMore = decltype(more)::value;
     constexpr bool kMasked = decltype(masked)::value;
-    constexpr int kNcw = nchunks(role);
     const int buf = kt & 1;
-    if constexpr (kMore) stage_load(kt + 1, role);
+    if constexpr (kMore) stage_load(kt + 1, vr);
     const uint16_t* const Kb = Ks + buf * KBUF;
     const uint16_t* const Vb = Vs + buf * VBUF;
-    // LEAN: one K and one V fragment set, each re-read right after its last reader (K of
-    // sub-block sb+1 after the last Q K^T on sb, V of sb after the last P V on sb-1)
-    constexpr bool kLean = (FORM & 1) != 0;
-    constexpr bool kLeanK = kLean;
-    short8_t kf[2][kNKT];
-    short8_t vf[2][2][kNDT];
+    // one K and one V fragment set, each re-read right after its last reader (K of sub-block
+    // sb+1 after the last Q K^T on sb, V of sb after the last P V on sb-1)
+    short8_t kf[kNKT];
+    short8_t vf[2][kNDT];
     f32x16_t S[2];
     short8_t pf[2][2];
-    read_k(Kb, 0, kf[0]);
-    read_v(Vb, 0, vf[0]);
-    auto kslot = [](int sb) { return kLeanK ? 0 : (sb & 1); };
-    auto vslot = [](int sb) { return kLean ? 0 : (sb & 1); };
+    read_k(Kb, 0, kf);
+    read_v(Vb, 0, vf);
     auto qk = [&](int x) __attribute__((always_inline)) {
-      const int sb = x / QB, b = x % QB;
+      const int b = x % QB;
       S[x & 1] = f32x16_t{};
 #pragma unroll
       for (int t = 0; t < kNKT; ++t) {
-        if constexpr (kF16 || H16) mma_f16(S[x & 1], kf[kslot(sb)][t], qf[b][t]);
-        else mma_bf16(S[x & 1], kf[kslot(sb)][t], qf[b][t]);
+        if constexpr (kF16 || H16) mma_f16(S[x & 1], kf[t], qf[b][t]);
+        else mma_bf16(S[x & 1], kf[t], qf[b][t]);
       }
     };
     auto pv = [&](int x) __attribute__((always_inline)) {
-      const int sb = x / QB, b = x % QB;
+      const int b = x % QB;
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
         for (int dt = 0; dt < kNDT; ++dt) {
-          if constexpr (H16) mma_f16(O[b][dt], vf[vslot(sb)][s2][dt], pf[x & 1][s2]);
-          else mma_bf16(O[b][dt], vf[vslot(sb)][s2][dt], pf[x & 1][s2]);
+          if constexpr (H16) mma_f16(O[b][dt], vf[s2][dt], pf[x & 1][s2]);
+          else mma_bf16(O[b][dt], vf[s2][dt], pf[x & 1][s2]);
         }
     };
     auto ex = [&](int x) __attribute__((always_inline)) {
@@ -454,72 +433,61 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
         }
     };
     qk(0);
-    if constexpr (SCHED) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     static_for<X>([&](auto xc) __attribute__((always_inline)) {
       constexpr int x = decltype(xc)::value;
-      // FORM bit 256: the younger half holds priority 1 for the first half of every kAlt steps
-      // (bit 512: kAlt = 4, else 2), so the two waves of a SIMD share the VALU evenly
-      // (bit 16384, with 512: priority 1 for 3 of every 4 steps)
-      if constexpr ((FORM & 256) != 0) {
-        constexpr int kAlt = (FORM & 512) ? 4 : 2;
-        constexpr int kOn = (FORM & 16384) ? 3 : kAlt / 2;
-        if constexpr (x % kAlt == 0) { if (young) __builtin_amdgcn_s_setprio(1); }
-        if constexpr (x % kAlt == kOn) { if (young) __builtin_amdgcn_s_setprio(0); }
-      }
+      // the younger half holds priority 1 for 3 of every 4 steps, so the two waves of a SIMD
+      // share the VALU evenly
+      if constexpr (x % 4 == 0) { if (young) __builtin_amdgcn_s_setprio(1); }
+      if constexpr (x % 4 == 3) { if (young) __builtin_amdgcn_s_setprio(0); }
       constexpr int sb = x / QB, b = x % QB;
-      // K of sub-block sb+1: LEAN after this step's Q K^T when it was the last one on sb
-      // (b == QB-2: Q K^T of block x+1 = (sb, QB-1)), else early into the other slot
-      // (QB == 1: block x+1 is already on sb+1, so its K is read at the start of this step)
-      constexpr bool kRdK = (kLeanK ? b == (QB >= 2 ? QB - 2 : 0) : b == 0) && sb + 1 < NSB;
-      constexpr bool kRdKEarly = kLeanK && kRdK && QB == 1;
-      // V: LEAN reads V(sb) after this step's P V on block x-1 = (sb-1, QB-1); else V(sb+1) early
-      constexpr bool kRdV = kLean ? (b == 0 && sb >= 1) : (b == (QB > 1 ? 1 : 0) && sb + 1 < NSB);
+      // K of sub-block sb+1: after this step's Q K^T when it was the last one on sb (b == QB-2:
+      // Q K^T of block x+1 = (sb, QB-1); QB == 1: block x+1 is already on sb+1, so its K is read
+      // at the start of this step)
+      constexpr bool kRdK = b == (QB >= 2 ? QB - 2 : 0) && sb + 1 < NSB;
+      constexpr bool kRdKEarly = kRdK && QB == 1;
+      // V(sb) after this step's P V on block x-1 = (sb-1, QB-1)
+      constexpr bool kRdV = b == 0 && sb >= 1;
       // the next tile's chunks go to the other buffer over the second half of the tile (every
       // wave has passed the barrier that ended the tile which last read that buffer)
       // chunks [c0, c1) of this thread are written in this step
       constexpr int kWn = kWe - kWs;
       constexpr bool kInW = x >= kWs && x < kWe;
-      constexpr int c0 = kInW ? ((x - kWs) * kNcw + kWn - 1) / kWn : 0;
-      constexpr int c1 = kInW ? ((x + 1 - kWs) * kNcw + kWn - 1) / kWn : 0;
+      constexpr int c0 = kInW ? ((x - kWs) * SCH + kWn - 1) / kWn : 0;
+      constexpr int c1 = kInW ? ((x + 1 - kWs) * SCH + kWn - 1) / kWn : 0;
       constexpr bool kStw = kMore && c1 > c0;
-      constexpr bool kStwK = kStw && decltype(role)::value != 2;   // the write converts K
-      if constexpr (!kLeanK && kRdK) read_k(Kb, sb + 1, kf[(sb + 1) & 1]);
-      if constexpr (kRdKEarly) read_k(Kb, sb + 1, kf[0]);
-      if constexpr (!kLean && kRdV) read_v(Vb, sb + 1, vf[(sb + 1) & 1]);
+      constexpr bool kStwK = kStw && !decltype(vr)::value;   // the write converts K
+      if constexpr (kRdKEarly) read_k(Kb, sb + 1, kf);
       if constexpr (x + 1 < X) qk(x + 1);
       ex(x);
-      if constexpr (kLeanK && kRdK && !kRdKEarly) read_k(Kb, sb + 1, kf[0]);
+      if constexpr (kRdK && !kRdKEarly) read_k(Kb, sb + 1, kf);
       if constexpr (x >= 1) pv(x - 1);
-      if constexpr (kLean && kRdV) read_v(Vb, sb, vf[0]);
+      if constexpr (kRdV) read_v(Vb, sb, vf);
       if constexpr (kStw)
 #pragma unroll
-        for (int i = c0; i < c1; ++i) stage_write(i, buf ^ 1, kF16, role);
-      if constexpr (SCHED) {
-        // one MFMA per slot (this step's Q K^T first, then P V), the step's exponentials and
-        // VALU spread evenly over the slots; LDS reads early, or (LEAN) after their last reader
-        // (masks: MFMA 0x8, VALU 0x2 -- which excludes the transcendental v_exp --, TRANS
-        // 0x400, DS_READ 0x100, DS_WRITE 0x200)
-        constexpr int nq = x + 1 < X ? kNKT : 0;
-        constexpr int nm = nq + (x >= 1 ? 2 * kNDT : 0);
-        constexpr int ne = 16;
-        constexpr int nv = 8 + (kF16 ? 0 : 16) + (kStwK && kF16 && !H16 ? 24 * (c1 - c0) : 0) + (kMasked ? 32 : 0);
-        constexpr int nr = (!kLeanK && kRdK ? kNKT : 0) + (!kLean && kRdV ? 4 * kNDT : 0);
-        if constexpr (kRdKEarly) __builtin_amdgcn_sched_group_barrier(0x100, kNKT, 0);
-        static_for<nm>([&](auto ic) __attribute__((always_inline)) {
-          constexpr int i = decltype(ic)::value;
-          constexpr int te = (ne * (i + 1)) / nm - (ne * i) / nm;
-          constexpr int tv = (nv * (i + 1)) / nm - (nv * i) / nm;
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x400, te, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, tv, 0);
-          if constexpr (nr > 0) __builtin_amdgcn_sched_group_barrier(0x100, (nr * (i + 1)) / nm - (nr * i) / nm, 0);
-          if constexpr (kLeanK && kRdK && !kRdKEarly && i >= nq && i < nq + kNKT)
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          if constexpr (kStw && i < 2) __builtin_amdgcn_sched_group_barrier(0x200, c1 - c0, 0);
-        });
-        if constexpr (kLean && kRdV) __builtin_amdgcn_sched_group_barrier(0x100, 4 * kNDT, 0);   // ds_read_b64_tr x2 per fragment
-        __builtin_amdgcn_sched_barrier(0);
-      }
+        for (int i = c0; i < c1; ++i) stage_write(i, buf ^ 1, kF16, vr);
+      // one MFMA per slot (this step's Q K^T first, then P V), the step's exponentials and
+      // VALU spread evenly over the slots; LDS reads after their last reader
+      // (masks: MFMA 0x8, VALU 0x2 -- which excludes the transcendental v_exp --, TRANS
+      // 0x400, DS_READ 0x100, DS_WRITE 0x200)
+      constexpr int nq = x + 1 < X ? kNKT : 0;
+      constexpr int nm = nq + (x >= 1 ? 2 * kNDT : 0);
+      constexpr int ne = 16;
+      constexpr int nv = 8 + (kF16 ? 0 : 16) + (kStwK && kCvtK ? 24 * (c1 - c0) : 0) + (kMasked ? 32 : 0);
+      if constexpr (kRdKEarly) __builtin_amdgcn_sched_group_barrier(0x100, kNKT, 0);
+      static_for<nm>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int i = decltype(ic)::value;
+        constexpr int te = (ne * (i + 1)) / nm - (ne * i) / nm;
+        constexpr int tv = (nv * (i + 1)) / nm - (nv * i) / nm;
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x400, te, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, tv, 0);
+        if constexpr (kRdK && !kRdKEarly && i >= nq && i < nq + kNKT)
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        if constexpr (kStw && i < 2) __builtin_amdgcn_sched_group_barrier(0x200, c1 - c0, 0);
+      });
+      if constexpr (kRdV) __builtin_amdgcn_sched_group_barrier(0x100, 4 * kNDT, 0);   // ds_read_b64_tr x2 per fragment
+      __builtin_amdgcn_sched_barrier(0);
     });
     pv(X - 1);
     stamp(2 + 2 * kt);
@@ -565,14 +533,13 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
   };
   constexpr std::false_type kNo{};
   constexpr std::true_type kYes{};
-  auto run_tiles = [&](auto role) __attribute__((always_inline)) {
-    for (int kt = 0; kt + 1 < ntiles; ++kt) tile(kt, kYes, kNo, role);
-    if (nfull == ntiles) tile(ntiles - 1, kNo, kNo, role);
-    else tile(ntiles - 1, kNo, kYes, role);
+  auto run_tiles = [&](auto vr) __attribute__((always_inline)) {
+    for (int kt = 0; kt + 1 < ntiles; ++kt) tile(kt, kYes, kNo, vr);
+    if (nfull == ntiles) tile(ntiles - 1, kNo, kNo, vr);
+    else tile(ntiles - 1, kNo, kYes, vr);
   };
-  if constexpr (!kSplit) run_tiles(std::integral_constant<int, 0>{});
-  else if (vrole) run_tiles(std::integral_constant<int, 2>{});
-  else run_tiles(std::integral_constant<int, 1>{});
+  if (vrole) run_tiles(kYes);
+  else run_tiles(kNo);
 
   {
     // a row sum can stay finite while an O element overflowed (p near 2^128 times a large |v|):
@@ -585,7 +552,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) nf = __builtin_fmaf(O[b][dt][r], 0.f, nf);   // NaN iff some O is inf/NaN
     bad |= !(nf == 0.f);
-    if constexpr (kU16Max) ovf |= kmag.x >= 0x4780 || kmag.y >= 0x4780;
+    if constexpr (kCvtK) ovf |= kmag.x >= 0x4780 || kmag.y >= 0x4780;
     const bool any_bad = __any(bad || ovf);
     if (lane == 0 && any_bad) atomicOr(&wg_flag, 1);
   }
@@ -698,38 +665,30 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 2 : 1) void self40_kernel(
   stamp(37);
 }
 
-template <int D, int WAVES, int QB, int BK, bool SCHED = true, int FORM = 0, bool H16 = false>
+template <int D, int WAVES, int QB, int BK, bool H16 = false, bool STAMPS = false>
 hipError_t launch(const SelfArgs& a, hipStream_t st) {
   SelfArgs b = a;
   b.n_qtiles = (a.P + 32 * QB * WAVES - 1) / (32 * QB * WAVES);
   dim3 grid(b.n_qtiles * a.H * a.N), block(64 * WAVES);
-  launch_kernel((self40_kernel<D, WAVES, QB, BK, SCHED, FORM, H16>), grid, block, 0, st, b);
+  launch_kernel((self40_kernel<D, WAVES, QB, BK, H16, STAMPS>), grid, block, 0, st, b);
   return hipGetLastError();
 }
 
 }  // namespace
 
-// every decision is p2p_select.h's: the forms below are the instantiations it names (FORM bits as
-// documented above the kernel; every other measured shape is in git history, DESIGN.md §4 and
-// profiles/ hold the logs)
+// every decision is p2p_select.h's: one line per kernel it names
 int launch_self40(const SelfArgs& a, SelfKernel k, hipStream_t st) {
-#ifdef S40_ONLY
-  return (int)launch<S40_ONLY>(a, st);
-#else
-  constexpr int kBase = 1 | 128 | 256 | 512 | 16384;
   switch (k) {
-    case SELF40_D40: return (int)launch<40, 8, 2, 256, true, kBase | 8388608>(a, st);
-    case SELF40_D40_H16: return (int)launch<40, 8, 2, 256, true, kBase, true>(a, st);
-    case SELF40_D40_ROUND3: return (int)launch<40, 8, 2, 256, true, kBase>(a, st);
-    case SELF40_D80: return (int)launch<80, 8, 1, 128, true, kBase>(a, st);
-    case SELF40_D80_H16: return (int)launch<80, 8, 1, 128, true, kBase, true>(a, st);
+    case SELF40_D40: return (int)launch<40, 8, 2, 256>(a, st);
+    case SELF40_D40_H16: return (int)launch<40, 8, 2, 256, true>(a, st);
+    case SELF40_D80: return (int)launch<80, 8, 1, 128>(a, st);
+    case SELF40_D80_H16: return (int)launch<80, 8, 1, 128, true>(a, st);
 #ifdef P2P_EXPERIMENTS
-    case SELF40_D40_STAMPS: return (int)launch<40, 8, 2, 256, true, 17281 | 8388608 | 16>(a, st);
-    case SELF40_D80_STAMPS: return (int)launch<80, 8, 1, 128, true, kBase | 16>(a, st);
+    case SELF40_D40_STAMPS: return (int)launch<40, 8, 2, 256, false, true>(a, st);
+    case SELF40_D80_STAMPS: return (int)launch<80, 8, 1, 128, false, true>(a, st);
 #endif
     default: return P2P_E_ARG;
   }
-#endif
 }
 
 }  // namespace p2p

@@ -519,15 +519,12 @@ hipError_t launch_ring(const SelfArgs& a, hipStream_t st) {
 }  // namespace
 
 // d = 160, bf16 inputs, O only: which K takes which form is p2p_select.h's (a split form covers
-// W x KBW x 32 keys; 3 x 2 and 4 x 2 are compiled but not selected: splitting K > 128 measured
-// slower than the per-tile kernels)
+// W x KBW x 32 keys, 128 at the most: splitting K > 128 measured slower than the per-tile kernels)
 int launch_self_split(const SelfArgs& a, SelfKernel k, hipStream_t st) {
   switch (k) {
     case SELF_SPLIT_1x1: return (int)launch_split<160, 1, 1>(a, st);
     case SELF_SPLIT_2x1: return (int)launch_split<160, 2, 1>(a, st);
     case SELF_SPLIT_2x2: return (int)launch_split<160, 2, 2>(a, st);
-    case SELF_SPLIT_3x2: return (int)launch_split<160, 3, 2>(a, st);
-    case SELF_SPLIT_4x2: return (int)launch_split<160, 4, 2>(a, st);
     case SELF_HALVES: {
       SelfArgs b = a;
       b.n_qtiles = (a.P + 63) / 64;

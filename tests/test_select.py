@@ -173,3 +173,35 @@ def test_select_header_is_host_only(tmp_path):
     csrc = os.path.join(ROOT, "prompt-to-prompt_amd", "csrc")
     subprocess.run([gxx, "-std=c++17", "-Wall", "-Werror", "-I", csrc, str(src), "-o", str(exe)], check=True)
     subprocess.run([str(exe)], check=True)
+
+
+def test_experiments_variant_switch_is_closed(tmp_path):
+    """An experiments build honours only the named P2P_SELF_VARIANT values: at the G1 shape 0 gives the
+    default kernel and 163 its stamped form; a value that names nothing (17281 once chose a kernel
+    that is gone) is P2P_E_ARG from select_self and select_cross, not the default kernel."""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++ on this machine")
+    src = tmp_path / "select_exp.cpp"
+    src.write_text('#include "p2p_select.h"\n'
+                   "static int self(int variant) {\n"
+                   "  return p2p::select_self(P2P_DTYPE_BF16, P2P_COMPUTE_BF16, 40, 4096, 4096, p2p::MODE_FUSED_, false,\n"
+                   "                          false, variant);\n"
+                   "}\n"
+                   "static int cross(int variant) {\n"
+                   "  return p2p::select_cross(P2P_DTYPE_BF16, P2P_COMPUTE_BF16, 40, 2, 8, 4096, 77, false, false, false,\n"
+                   "                           variant);\n"
+                   "}\n"
+                   "int main() {\n"
+                   "  if (self(0) != p2p::SELF40_D40) return 1;\n"
+                   "  if (self(163) != p2p::SELF40_D40_STAMPS) return 2;\n"
+                   "  if (self(17281) != P2P_E_ARG) return 3;\n"
+                   "  if (cross(0) != p2p::CROSS_GROUP) return 4;\n"
+                   "  if (cross(5) != P2P_E_ARG) return 5;\n"
+                   "  return 0;\n"
+                   "}\n")
+    exe = tmp_path / "select_exp"
+    csrc = os.path.join(ROOT, "prompt-to-prompt_amd", "csrc")
+    subprocess.run([gxx, "-std=c++17", "-Wall", "-Werror", "-DP2P_EXPERIMENTS", "-I", csrc, str(src), "-o", str(exe)],
+                   check=True)
+    assert subprocess.run([str(exe)]).returncode == 0

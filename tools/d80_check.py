@@ -1,5 +1,6 @@
 """d = 80 self-attention parity probe (experiments build): max |O - ref| / bound for the cases of
-tests/test_gpu_kernels.py::test_self_attention_d80_pipelined under P2P_SELF_VARIANT."""
+tests/test_gpu_kernels.py::test_self_attention_d80_pipelined (P2P_SELF_VARIANT=164 in the environment
+checks the stamped kernel instead of the default)."""
 import os
 import sys
 

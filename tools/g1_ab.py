@@ -1,5 +1,7 @@
-"""A/B of the G1/G7 self-attention kernel schedules (one variant per process: the experiments
-build reads P2P_SELF_VARIANT once at load).  Checks the variant against a torch fp32 reference on
+"""Check and time the G1/G7 self-attention kernel, one P2P_SELF_VARIANT per process (the experiments
+build reads it once at load; the values that exist are p2p_select.h's Variant: 0 = the default
+kernel, 163 = the same with clock stamps, 164 its d = 80 counterpart with G1AB_SHAPE=1024,80; the
+library refuses any other).  Checks the kernel against a torch fp32 reference on
 the same bf16 inputs (plain, peaky rows, a source-map remap, ragged P/K), then times the config-2
 G1 launch (N = 8, H = 8, P = K = 4096, d = 40) with HIP events: median of 7 rounds x 50 launches.
 Usage: P2P_EXPERIMENTS_LIB=1 P2P_SELF_VARIANT=v python tools/g1_ab.py"""

@@ -1,6 +1,7 @@
 """Launch only the dominant kernel (G1/G7 self-attention: P = K = 4096, d = 40, N = 8, H = 8,
 bf16) a fixed number of times -- the program rocprofv3 --pmc passes profile.
-Usage: python tools/g1_only.py [launches] [P] [d]; P2P_SELF_VARIANT selects the kernel variant."""
+Usage: python tools/g1_only.py [launches] [P] [d]   (experiments library: P2P_SELF_VARIANT=163 / 164
+runs the stamped d = 40 / 80 kernel)"""
 import os
 import sys
 

@@ -22,6 +22,9 @@
 #     g1shape:<v>:<P,d>      tools/g1_ab.py (correctness + isolated timing) of variant v at shape P,d (experiments lib)
 #     variants:<v1,v2,..>[:<prefix>]  in-pipeline A/B: a short bench.py per P2P_SELF_VARIANT (experiments lib),
 #                            printing the HIP-event average of every attention geometry (starting with <prefix>)
+#   P2P_SELF_VARIANT values (<v> above; csrc/p2p_select.h's Variant): 0 the default kernels, 90 cross
+#   stamps, 123 group stamps, 163 / 164 self40 stamps at d = 40 / 80.  The experiments library refuses any
+#   other value (P2P_E_ARG), so an A/B over a value that no longer exists fails instead of timing the default twice.
 set -u
 export TMPDIR=/tmp
 tag=$1; shift

@@ -3,8 +3,8 @@
 tile, recompute check + epilogue, and the launch timeline.  Stamps of the first S40_NWG (512) workgroups of a config-2 G1
 launch (N = 8, H = 8, P = K = 4096, d = 40).
 Usage: P2P_EXPERIMENTS_LIB=1 P2P_SELF_VARIANT=163 python tools/s40_stamps.py
-       S40_STAMPS=P,d,waves,bk,qb (default 4096,40,8,256,2; the d = 80 stamped variant 103:
-       S40_STAMPS=1024,80,4,128,2)"""
+       S40_STAMPS=P,d,waves,bk,qb (default 4096,40,8,256,2; the d = 80 stamped kernel, variant 164:
+       S40_STAMPS=1024,80,8,128,1)"""
 import ctypes
 import os
 import statistics

@@ -1,7 +1,8 @@
 """Self-attention launch timing at the small SD geometries (config-2 U-Net call: N = 8, H = 8,
 bf16 IO, O only): G2 (P = K = 1024, d = 80), G3 (256, 160), G4 (64, 160).  GPU time per launch
 from captured HIP graphs (no host enqueue), median of 5 replays x 50 launches.
-Usage: [P2P_EXPERIMENTS_LIB=1 P2P_SELF_VARIANT=v] python tools/small_bench.py"""
+Usage: [P2P_EXPERIMENTS_LIB=1 P2P_SELF_VARIANT=164] python tools/small_bench.py   (164: G2 on the stamped
+kernel; G3 / G4 have no variant)"""
 import json
 import os
 import statistics

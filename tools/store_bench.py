@@ -33,7 +33,7 @@ def timeit(fn, iters=20):
 def main():
     """The running sums rotate over enough buffers (>= 1 GiB) that none stays in the 256 MB
     Infinity Cache between its launches -- as in the pipeline, where five G2/G6 layers keep 670 MB
-    of self maps.  P2P_SELF_VARIANT=6 times the maps kernel with plain (temporal) accesses."""
+    of self maps."""
     N, H, B = 8, 8, 4
     for P, d in ((1024, 80), (256, 160)):
         C = H * d
@@ -53,12 +53,9 @@ def main():
         plain = timeit(lambda: _hip.self_attn(q, k, v, o, H, d ** -0.5))
         res = {"P": P, "d": d, "fused_us": round(plain, 1), "map_bytes_MB": round(2 * map_bytes / 1e6, 1),
                "rotating_buffers": nbuf}
-        for name, var in (("store_us", "0"), ("store_us_plain_access", "6")):
-            os.environ["P2P_SELF_VARIANT"] = var
-            t = timeit(stored, iters=4 * nbuf)
-            res[name] = round(t, 1)
-            res[name.replace("_us", "_GBps")] = round((2.0 * map_bytes + 4 * N * P * C * 2) / t / 1e3, 1)
-        os.environ["P2P_SELF_VARIANT"] = "0"
+        t = timeit(stored, iters=4 * nbuf)
+        res["store_us"] = round(t, 1)
+        res["store_GBps"] = round((2.0 * map_bytes + 4 * N * P * C * 2) / t / 1e3, 1)
         print(json.dumps(res), flush=True)
         del stores
         torch.cuda.empty_cache()
