@@ -406,6 +406,56 @@ typedef struct {
 
 int p2p_image_to_model(const p2p_image_to_model_args* a, p2p_stream_t stream);
 
+/* The CLIP text encoder (p2p_amd/text_encoder.py; ptp_utils.py:151,156 call it through
+ * model.text_encoder), additive to ABI 16.  The three entry points below take 16-bit tensors only
+ * (P2P_DTYPE_BF16 / P2P_DTYPE_F16, anything else is P2P_E_DTYPE), compute in f32 with one rounding
+ * at the store, and reduce in a fixed order: bit-identical from launch to launch. */
+
+/* Causal self-attention over the prompt tokens: O = softmax(causal(Q K^T * scale)) V, token i
+ * attending to tokens <= i.  There is no padding mask.  The tokens x tokens matrix is never
+ * written.  Rejected before anything is launched: n_query != n_key (P2P_E_ARG), more than
+ * P2P_MAX_KEYS_CROSS tokens (P2P_E_KEYS), head_dim != 64 (P2P_E_HEAD_DIM), f32 tensors or
+ * compute = P2P_COMPUTE_F32 (P2P_E_DTYPE), a pointer or stride off 16 bytes (P2P_E_ALIGN).
+ * bf16 inputs run on bf16 MFMAs, fp16 inputs on f16 MFMAs. */
+int p2p_causal_attn_fwd(const p2p_attn_tensors* t, p2p_stream_t stream);
+
+/* nn.LayerNorm over rows of `channels` elements with the residual add in front of it:
+ *   s = x + add + add_bias          (f32, left to right), rounded once to dtype
+ *   sum_out = s                     (nullable; may alias x: the residual stream updated in place)
+ *   y = (s - mean) * rstd * gamma + beta
+ * with the mean and the centred, biased variance (both f32, as p2p_group_norm) taken from the
+ * ROUNDED s -- the values the next reader of sum_out sees -- so the residual stream and its
+ * normalised copy stay consistent.  Dense tensors, 16-byte aligned pointers; channels % 8 == 0
+ * (else P2P_E_ALIGN) and channels <= 2048 (else P2P_E_ARG). */
+typedef struct {
+  const void* x;         /* [rows, channels]                                  */
+  const void* add;       /* nullable [rows, channels]: a GEMM's output        */
+  const void* add_bias;  /* nullable [channels]: that GEMM's bias             */
+  const void* gamma;     /* [channels]                                        */
+  const void* beta;      /* [channels]                                        */
+  void* sum_out;         /* nullable [rows, channels]                         */
+  void* y;               /* [rows, channels]                                  */
+  int32_t rows, channels;
+  float eps;
+  int32_t dtype;         /* P2P_DTYPE_BF16 / P2P_DTYPE_F16: every tensor      */
+} p2p_layer_norm_args;
+
+int p2p_layer_norm(const p2p_layer_norm_args* a, p2p_stream_t stream);
+
+/* Bias + quick-GELU behind a GEMM run without its bias: out[m, j] = h * sigmoid(1.702 h),
+ * h = in[m, j] + bias[j], j < d.  Row strides in elements, multiples of 8 (as d), >= d; out may
+ * be in. */
+typedef struct {
+  const void* in;
+  const void* bias;  /* [d] */
+  void* out;
+  int64_t in_row_stride, out_row_stride;
+  int32_t rows, d;
+  int32_t dtype;
+} p2p_bias_act_args;
+
+int p2p_bias_quick_gelu(const p2p_bias_act_args* a, p2p_stream_t stream);
+
 /* Measurement only (ABI 15; bench.py's roofline clock, not part of the reference's interface):
  * n_workgroups one-wave workgroups each read the shader-cycle counter and the constant 100 MHz
  * counter, spin until `ticks` (1..1e6) of the 100 MHz counter have passed, and read both again:

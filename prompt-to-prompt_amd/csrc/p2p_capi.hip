@@ -417,6 +417,33 @@ int p2p_image_to_model(const p2p_image_to_model_args* a, p2p_stream_t stream) {
   return run_image_to_model(*a, (hipStream_t)stream);
 }
 
+int p2p_causal_attn_fwd(const p2p_attn_tensors* t, p2p_stream_t stream) {
+  const int rc = check_tensors(t, true, true, true, true);
+  if (rc) return rc;
+  if (t->n_query != t->n_key) return P2P_E_ARG;
+  if (t->n_key > P2P_MAX_KEYS_CROSS) return P2P_E_KEYS;
+  if (t->head_dim != 64) return P2P_E_HEAD_DIM;
+  // (check_tensors has rejected 16-bit tensors with the exact-f32 check mode)
+  if (t->io_dtype != P2P_DTYPE_BF16 && t->io_dtype != P2P_DTYPE_F16) return P2P_E_DTYPE;
+  CausalArgs a;
+  a.q = t->q; a.k = t->k; a.v = t->v; a.o = t->o;
+  a.ldq = t->q_row_stride; a.ldk = t->k_row_stride; a.ldv = t->v_row_stride; a.ldo = t->o_row_stride;
+  a.bsq = t->q_batch_stride; a.bsk = t->k_batch_stride; a.bsv = t->v_batch_stride; a.bso = t->o_batch_stride;
+  a.N = t->n_batch; a.T = t->n_key; a.H = t->n_heads;
+  a.scale_log2 = t->scale * 1.4426950408889634f;
+  return run_causal_attn(a, t->io_dtype, (hipStream_t)stream);
+}
+
+int p2p_layer_norm(const p2p_layer_norm_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_layer_norm(*a, (hipStream_t)stream);
+}
+
+int p2p_bias_quick_gelu(const p2p_bias_act_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_bias_quick_gelu(*a, (hipStream_t)stream);
+}
+
 int p2p_clock_probe(uint64_t* out, int32_t n_workgroups, int32_t ticks, p2p_stream_t stream) {
   if (!out || n_workgroups < 1 || n_workgroups > 1024 || ticks < 1 || ticks > 1000000) return P2P_E_ARG;
   return run_clock_probe(reinterpret_cast<unsigned long long*>(out), n_workgroups, ticks, (hipStream_t)stream);

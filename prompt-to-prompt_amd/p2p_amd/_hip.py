@@ -134,6 +134,22 @@ class GegluArgs(ctypes.Structure):
     ]
 
 
+class LayerNormArgs(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("add", ctypes.c_void_p), ("add_bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
+        ("beta", ctypes.c_void_p), ("sum_out", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("rows", ctypes.c_int32), ("channels", ctypes.c_int32), ("eps", ctypes.c_float), ("dtype", ctypes.c_int32),
+    ]
+
+
+class BiasActArgs(ctypes.Structure):
+    _fields_ = [
+        ("inp", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("in_row_stride", ctypes.c_int64), ("out_row_stride", ctypes.c_int64),
+        ("rows", ctypes.c_int32), ("d", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
 class ImageU8Args(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("out", ctypes.c_void_p), ("n", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -184,6 +200,9 @@ def lib():
         L.p2p_group_norm_stats_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_bias_residual.argtypes = [ctypes.POINTER(BiasResidualArgs), vp]
         L.p2p_geglu.argtypes = [ctypes.POINTER(GegluArgs), vp]
+        L.p2p_causal_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp]
+        L.p2p_layer_norm.argtypes = [ctypes.POINTER(LayerNormArgs), vp]
+        L.p2p_bias_quick_gelu.argtypes = [ctypes.POINTER(BiasActArgs), vp]
         L.p2p_image_u8.argtypes = [ctypes.POINTER(ImageU8Args), vp]
         L.p2p_image_to_model.argtypes = [ctypes.POINTER(ImageToModelArgs), vp]
         L.p2p_clock_probe.argtypes = [vp, i32, i32, vp]
@@ -214,7 +233,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_attn_fwd_lse", "p2p_attn_bwd", "p2p_attn_bwd_workspace", "p2p_clock_probe",
                     "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu",
                     "p2p_self_attn_kernel", "p2p_cross_attn_kernel", "p2p_plms_step", "p2p_image_u8",
-                    "p2p_image_to_model", "p2p_group_norm_stats_floats")
+                    "p2p_image_to_model", "p2p_group_norm_stats_floats", "p2p_causal_attn_fwd", "p2p_layer_norm",
+                    "p2p_bias_quick_gelu")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -618,7 +638,7 @@ def attn_bwd(q, k, v, o, dout, lse, heads, scale, dq, dk, dv, delta, workspace=N
 # -- U-Net glue (p2p_unet.hip).  Each returns its output, or None when the library reports the
 # arguments unsupported (dtype, alignment) or the tensors are not dense: the caller then runs
 # its torch lines.  Any other rejection raises.
-P2P_E_HEAD_DIM, P2P_E_DTYPE, P2P_E_ALIGN = -2, -3, -6
+P2P_E_HEAD_DIM, P2P_E_DTYPE, P2P_E_KEYS, P2P_E_ALIGN = -2, -3, -4, -6
 ACT_NONE, ACT_SILU = 0, 1
 LAYOUT_NCHW, LAYOUT_TOKENS = 0, 1
 
@@ -750,3 +770,71 @@ def image_to_model(img: torch.Tensor, dtype: torch.dtype):
     a.n, a.height, a.width, a.dtype = N, H, W, _dtype_code(out)
     ok = _glue_rc(lib().p2p_image_to_model(ctypes.byref(a), _stream(img.device)), "p2p_image_to_model")
     return out if ok else None
+
+
+# -- the text encoder (p2p_text.hip).  As the glue above: None where the library reports the dtype,
+# shape or alignment unsupported -- or the tensors are not on the GPU -- and the caller runs its
+# torch lines; any other rejection raises.
+LN_MAX_CHANNELS = 2048
+
+
+def causal_attn(q, k, v, heads: int, scale: float):
+    """softmax(causal(q k^T * scale)) v for q / k / v [N, T, heads * 64] with a unit last stride
+    (strided views of one QKV GEMM output are served as they are), T <= MAX_KEYS_CROSS
+    (p2p_causal_attn_fwd).  Returns a dense [N, T, heads * 64] tensor."""
+    if not (q.is_cuda and k.is_cuda and v.is_cuda) or q.dtype not in (torch.bfloat16, torch.float16):
+        return None
+    o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    for n0 in range(0, q.shape[0], MAX_BATCH):     # the library takes MAX_BATCH entries per launch
+        sl = slice(n0, n0 + MAX_BATCH)
+        t = make_tensors(q[sl], k[sl], v[sl], o[sl], heads, scale, "bf16")
+        rc = lib().p2p_causal_attn_fwd(ctypes.byref(t), _stream(q.device))
+        if rc in (P2P_E_HEAD_DIM, P2P_E_KEYS, P2P_E_DTYPE, P2P_E_ALIGN):
+            return None                            # decided from the shapes: the first chunk's answer is every chunk's
+        _check(rc, "p2p_causal_attn_fwd")
+    return o
+
+
+def layer_norm(x, gamma, beta, eps: float, add=None, add_bias=None, sum_out=None):
+    """LayerNorm(x + add + add_bias) * gamma + beta over the last dimension (p2p_layer_norm).  x, add:
+    dense [..., C]; add_bias, gamma, beta: [C]; sum_out: None, or a dense tensor like x (x itself is
+    allowed) that receives the rounded sum.  Returns y, shaped like x."""
+    C = x.shape[-1]
+    ts = [t for t in (x, add, add_bias, gamma, beta, sum_out) if t is not None]
+    if not all(t.is_cuda and t.dtype == x.dtype and t.is_contiguous() for t in ts) or C > LN_MAX_CHANNELS:
+        return None
+    if (add is not None and add.shape != x.shape) or (sum_out is not None and sum_out.shape != x.shape):
+        raise HipError(f"layer_norm: add / sum_out do not match x {tuple(x.shape)}")
+    a = LayerNormArgs()
+    a.x = x.data_ptr()
+    a.add = add.data_ptr() if add is not None else None
+    a.add_bias = _vec(add_bias, x, C).data_ptr() if add_bias is not None else None
+    a.gamma, a.beta = _vec(gamma, x, C).data_ptr(), _vec(beta, x, C).data_ptr()
+    a.sum_out = sum_out.data_ptr() if sum_out is not None else None
+    y = torch.empty_like(x)
+    a.y = y.data_ptr()
+    a.rows, a.channels = x.numel() // C, C
+    a.eps = float(eps)
+    a.dtype = _glue_dtype(x)
+    return y if _glue_rc(lib().p2p_layer_norm(ctypes.byref(a), _stream(x.device)), "p2p_layer_norm") else None
+
+
+def bias_quick_gelu(x, bias, out=None):
+    """h * sigmoid(1.702 h), h = x + bias, for x [..., D] with a unit last stride (p2p_bias_quick_gelu);
+    ``out``: None (a new dense tensor) or x itself (in place)."""
+    D = x.shape[-1]
+    if not (x.is_cuda and bias.is_cuda) or bias.dtype != x.dtype:
+        return None
+    x2 = x.reshape(-1, D)     # a view for the dense and row-strided inputs served here
+    if x2.stride(-1) != 1 or x2.data_ptr() != x.data_ptr():
+        return None
+    if out is not None and out is not x:
+        raise HipError("bias_quick_gelu: out is None or the input itself")
+    res = x if out is x else x.new_empty(x.shape)
+    g = BiasActArgs()
+    g.inp, g.bias, g.out = x2.data_ptr(), _vec(bias, x, D).data_ptr(), res.data_ptr()
+    g.in_row_stride = x2.stride(0) if x2.shape[0] > 1 else D
+    g.out_row_stride = g.in_row_stride if out is x else D
+    g.rows, g.d = x2.shape[0], D
+    g.dtype = _glue_dtype(x)
+    return res if _glue_rc(lib().p2p_bias_quick_gelu(ctypes.byref(g), _stream(x.device)), "p2p_bias_quick_gelu") else None

@@ -5,7 +5,8 @@ No checkpoints, tokenizer vocabularies or text encoders are available offline, s
 ``text_encoder``, ``unet``, ``scheduler``, ``device``; main.py:29) is assembled from
 stand-ins: the deterministic tokenizer, a seeded embedding-table text encoder that maps
 identical prompts to identical contexts (as CLIP does for the shared "" uncond rows), the
-random-init SD-shaped U-Net and the DDIM scheduler of null_text.py:16-20.
+random-init SD-shaped U-Net and the DDIM scheduler of null_text.py:16-20.  On request the
+stand-in encoder gives way to the random-init SD-shaped CLIP text transformer (text_encoder.py).
 """
 from __future__ import annotations
 
@@ -41,17 +42,23 @@ class SyntheticStableDiffusion:
     random-init SD-shaped ``vae.AutoencoderKL`` (or, with ``vae_config``, one of those keyword
     arguments) in the U-Net's dtype, so that text2image_ldm_stable returns images and NullInversion
     takes one; the default has none and works on latents.  It is built last: the seeded weights of
-    everything else are the same with and without it."""
+    everything else are the same with and without it.  ``text_encoder``: build the random-init
+    SD-shaped ``text_encoder.CLIPTextModel`` (or, with ``text_encoder_config``, one of those keyword
+    arguments) in the U-Net's dtype in place of the embedding-table stand-in, so that a context row
+    depends causally on every earlier token, as CLIP's does.  It is built after everything else, from
+    a generator of its own: the U-Net's and the VAE's weights do not change with it."""
 
     def __init__(self, device="cuda", dtype=torch.float32, seed=0, scheduler="ddim", unet_config=None,
-                 vae=False, vae_config=None):
+                 vae=False, vae_config=None, text_encoder=False, text_encoder_config=None):
         self.device = torch.device(device)
         self.tokenizer = default_tokenizer()
         torch.manual_seed(seed)
         self.unet = UNet2DConditionModel(**(unet_config or {})).to(self.device, dtype).eval()
         for p in self.unet.parameters():
             p.requires_grad_(False)
-        self.text_encoder = SyntheticTextEncoder().to(self.device)
+        clip = text_encoder or text_encoder_config is not None
+        # (the stand-in draws from a generator of its own: leaving it out moves no other weight)
+        self.text_encoder = None if clip else SyntheticTextEncoder().to(self.device)
         if scheduler == "ddim":
             self.scheduler = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                                            clip_sample=False, set_alpha_to_one=False)
@@ -65,6 +72,12 @@ class SyntheticStableDiffusion:
             from .vae import AutoencoderKL
             self.vae = AutoencoderKL(**(vae_config or {})).to(self.device, dtype).eval()
             for p in self.vae.parameters():
+                p.requires_grad_(False)
+        if clip:
+            from .text_encoder import CLIPTextModel
+            g = torch.Generator().manual_seed(seed + 1)
+            self.text_encoder = CLIPTextModel(**(text_encoder_config or {}), generator=g).to(self.device, dtype).eval()
+            for p in self.text_encoder.parameters():
                 p.requires_grad_(False)
 
 
