@@ -456,6 +456,25 @@ typedef struct {
 
 int p2p_bias_quick_gelu(const p2p_bias_act_args* a, p2p_stream_t stream);
 
+/* The LDMBert text encoder of LDM-256 (p2p_amd/ldm_bert.py; ptp_utils.py:98-126 call it through
+ * model.bert), additive to ABI 16: the two entry points below beside p2p_layer_norm, under the
+ * same rules (16-bit tensors, f32 arithmetic, one rounding at the store, a fixed reduction order). */
+
+/* Bidirectional self-attention over the prompt tokens: O = softmax(Q K^T * scale) V, with the
+ * operands, limits and rejections of p2p_causal_attn_fwd.  key_counts: NULL -- every entry attends
+ * to all n_key tokens (the reference passes no attention mask) -- or a device array of n_batch
+ * int32 counts (4-byte aligned, else P2P_E_ALIGN): entry n attends to keys < key_counts[n] only
+ * (right padding), and all n_query rows are still computed and stored.  A key at or past the
+ * count contributes exactly 0 and is never read from memory.  The counts live on the device, so a
+ * count outside [1, n_key] cannot be seen, let alone rejected, by the host: the kernel clamps it
+ * into [1, n_key], and no row is ever empty. */
+int p2p_text_attn_fwd(const p2p_attn_tensors* t, const int32_t* key_counts, p2p_stream_t stream);
+
+/* Bias + exact (erf) GELU behind a GEMM run without its bias: out[m, j] = 0.5 h (1 + erf(h / sqrt 2)),
+ * h = in[m, j] + bias[j], j < d.  Arguments, vector widths, in-place rule and rejections as
+ * p2p_bias_quick_gelu. */
+int p2p_bias_gelu(const p2p_bias_act_args* a, p2p_stream_t stream);
+
 /* Measurement only (ABI 15; bench.py's roofline clock, not part of the reference's interface):
  * n_workgroups one-wave workgroups each read the shader-cycle counter and the constant 100 MHz
  * counter, spin until `ticks` (1..1e6) of the 100 MHz counter have passed, and read both again:

@@ -417,7 +417,8 @@ int p2p_image_to_model(const p2p_image_to_model_args* a, p2p_stream_t stream) {
   return run_image_to_model(*a, (hipStream_t)stream);
 }
 
-int p2p_causal_attn_fwd(const p2p_attn_tensors* t, p2p_stream_t stream) {
+// the two text-encoder attention entries: the same checks, the same kernel arguments
+static int text_attn_fwd(const p2p_attn_tensors* t, bool causal, const int32_t* key_counts, p2p_stream_t stream) {
   const int rc = check_tensors(t, true, true, true, true);
   if (rc) return rc;
   if (t->n_query != t->n_key) return P2P_E_ARG;
@@ -425,13 +426,23 @@ int p2p_causal_attn_fwd(const p2p_attn_tensors* t, p2p_stream_t stream) {
   if (t->head_dim != 64) return P2P_E_HEAD_DIM;
   // (check_tensors has rejected 16-bit tensors with the exact-f32 check mode)
   if (t->io_dtype != P2P_DTYPE_BF16 && t->io_dtype != P2P_DTYPE_F16) return P2P_E_DTYPE;
-  CausalArgs a;
+  if ((uintptr_t)key_counts & 3) return P2P_E_ALIGN;
+  TextAttnArgs a;
   a.q = t->q; a.k = t->k; a.v = t->v; a.o = t->o;
   a.ldq = t->q_row_stride; a.ldk = t->k_row_stride; a.ldv = t->v_row_stride; a.ldo = t->o_row_stride;
   a.bsq = t->q_batch_stride; a.bsk = t->k_batch_stride; a.bsv = t->v_batch_stride; a.bso = t->o_batch_stride;
   a.N = t->n_batch; a.T = t->n_key; a.H = t->n_heads;
   a.scale_log2 = t->scale * 1.4426950408889634f;
-  return run_causal_attn(a, t->io_dtype, (hipStream_t)stream);
+  a.key_counts = key_counts;
+  return run_text_attn(a, causal, t->io_dtype, (hipStream_t)stream);
+}
+
+int p2p_causal_attn_fwd(const p2p_attn_tensors* t, p2p_stream_t stream) {
+  return text_attn_fwd(t, true, nullptr, stream);
+}
+
+int p2p_text_attn_fwd(const p2p_attn_tensors* t, const int32_t* key_counts, p2p_stream_t stream) {
+  return text_attn_fwd(t, false, key_counts, stream);
 }
 
 int p2p_layer_norm(const p2p_layer_norm_args* a, p2p_stream_t stream) {
@@ -441,7 +452,12 @@ int p2p_layer_norm(const p2p_layer_norm_args* a, p2p_stream_t stream) {
 
 int p2p_bias_quick_gelu(const p2p_bias_act_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
-  return run_bias_quick_gelu(*a, (hipStream_t)stream);
+  return run_bias_act(*a, false, (hipStream_t)stream);
+}
+
+int p2p_bias_gelu(const p2p_bias_act_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_bias_act(*a, true, (hipStream_t)stream);
 }
 
 int p2p_clock_probe(uint64_t* out, int32_t n_workgroups, int32_t ticks, p2p_stream_t stream) {

@@ -177,9 +177,10 @@ int run_geglu(const p2p_geglu_args& a, hipStream_t st);
 // the image ends (p2p_image.hip): every argument check happens in these, before the launch
 int run_image_u8(const p2p_image_u8_args& a, hipStream_t st);
 int run_image_to_model(const p2p_image_to_model_args& a, hipStream_t st);
-// the text encoder's kernels (p2p_text.hip).  causal_attn_kernel: head dim 64, T <= P2P_MAX_KEYS_CROSS
-// tokens, bf16 / fp16 inputs (p2p_causal_attn_fwd checks all of it before filling these)
-struct CausalArgs {
+// the text encoders' kernels (p2p_text.hip).  text_attn_kernel: head dim 64, T <= P2P_MAX_KEYS_CROSS
+// tokens, bf16 / fp16 inputs (p2p_causal_attn_fwd and p2p_text_attn_fwd check all of it before
+// filling these)
+struct TextAttnArgs {
   const void* q;
   const void* k;
   const void* v;
@@ -188,11 +189,12 @@ struct CausalArgs {
   int64_t bsq, bsk, bsv, bso;  // batch strides (elements)
   int N, T, H;
   float scale_log2;            // scale * log2(e)
+  const int32_t* key_counts;   // bidirectional only: null, or N device counts (clamped into [1, T])
 };
-int run_causal_attn(const CausalArgs& a, int io_dtype, hipStream_t st);
+int run_text_attn(const TextAttnArgs& a, bool causal, int io_dtype, hipStream_t st);
 // every argument check happens in these, before the launch
 int run_layer_norm(const p2p_layer_norm_args& a, hipStream_t st);
-int run_bias_quick_gelu(const p2p_bias_act_args& a, hipStream_t st);
+int run_bias_act(const p2p_bias_act_args& a, bool erf, hipStream_t st);   // quick-GELU, or the erf GELU
 int run_clock_probe(unsigned long long* out, int n_wg, int ticks, hipStream_t st);
 
 }  // namespace p2p

@@ -1,17 +1,22 @@
-// The CLIP text encoder's own kernels (p2p_amd/text_encoder.py): causal self-attention over the
-// <= 96 prompt tokens at head dim 64, LayerNorm with the residual add and a GEMM's bias in front of
-// it, and bias + quick-GELU behind fc1.  16-bit I/O (bf16 or f16), f32 arithmetic, one rounding at
-// the store; every reduction runs in a fixed order (no atomics), so two launches on the same input
-// are bit-identical.
+// The text encoders' own kernels (p2p_amd/text_encoder.py: CLIP; p2p_amd/ldm_bert.py: LDMBert):
+// self-attention over the <= 96 prompt tokens at head dim 64 -- causal for CLIP, bidirectional with
+// an optional per-entry key count for LDMBert -- LayerNorm with the residual add and a GEMM's bias
+// in front of it, and bias + quick-GELU (CLIP) or bias + erf-GELU (LDMBert) behind fc1.  16-bit I/O
+// (bf16 or f16), f32 arithmetic, one rounding at the store; every reduction runs in a fixed order
+// (no atomics), so two launches on the same input are bit-identical.
 //
-// causal_attn_kernel follows the transposed-fragment convention of p2p_device.h (S^T = K Q^T and
+// text_attn_kernel follows the transposed-fragment convention of p2p_device.h (S^T = K Q^T and
 // O^T = V^T P^T, query on the lane) and the staging of cross_attn_kernel's lean path: one
 // workgroup per (batch entry, head) stages K and V once -- K row-major with KStride rows for the
 // ds_read_b128 fragment loads, V row-major with VStrideBf16 rows for ds_read_b64_tr_b16 -- and wave
-// w owns queries 32 w .. 32 w + 31.  Causality is the loop bound: wave w visits key blocks 0 .. w
-// (six of the nine 32 x 32 blocks of a 96 x 96 tile), and only its diagonal block is masked.  The
-// waves' work is 1 : 2 : 3 blocks; pairing blocks to even it out was not tried.
-// The T x T matrix lives in registers only.
+// w owns queries 32 w .. 32 w + 31.  CAUSAL: causality is the loop bound: wave w visits key blocks
+// 0 .. w (six of the nine 32 x 32 blocks of a 96 x 96 tile), and only its diagonal block is masked.
+// The waves' work is 1 : 2 : 3 blocks; pairing blocks to even it out was not tried (DESIGN.md
+// §4.13).  Keys T .. 95 are zero rows of the LDS tile, which causality hides from every stored row.
+// !CAUSAL: an entry attends to its first L keys (L = T, or its key count clamped into [1, T]);
+// every wave visits every key block below L, an even split, and nothing hides the zero rows L .. 95
+// -- they would score 0, not -inf -- so the block that holds key L masks them by index.  Either
+// way the T x T matrix lives in registers only.
 #include "p2p_device.h"
 #include "p2p_kernels.h"
 
@@ -36,8 +41,8 @@ __device__ __forceinline__ float round_p(MmaF16, float p) { return h2f(f2h(p)); 
 constexpr int kCausalD = 64;
 constexpr int kCausalWaves = P2P_MAX_KEYS_CROSS / 32;
 
-template <typename IO, typename MQ, typename MP>
-__global__ __launch_bounds__(64 * kCausalWaves) void causal_attn_kernel(CausalArgs a) {
+template <bool CAUSAL, typename IO, typename MQ, typename MP>
+__global__ __launch_bounds__(64 * kCausalWaves) void text_attn_kernel(TextAttnArgs a) {
   using EK = typename MQ::elem;
   using EV = typename MP::elem;
   constexpr int D = kCausalD;
@@ -68,6 +73,9 @@ __global__ __launch_bounds__(64 * kCausalWaves) void causal_attn_kernel(CausalAr
   const int T = a.T;
   const int p = wave * 32 + qi;
   const bool prow = p < T;
+  // the keys this entry attends to (workgroup-uniform).  L >= 1: key 0 is always visible
+  int L = T;
+  if (!CAUSAL && a.key_counts) L = min(max(a.key_counts[n], 1), T);
 
   // every global load first: this lane's Q fragments, this thread's K and V chunks
   typename MQ::frag qf[NKT];
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(64 * kCausalWaves) void causal_attn_kernel(CausalAr
     const int cidx = tid + i * NT;
     const int row = cidx / CPR;
     const int ch = cidx - row * CPR;
-    if (row < T) {   // rows T .. 95 are never read from memory: their LDS rows are zero
+    if (row < L) {   // rows L .. 95 are never read from memory: their LDS rows are zero
       kc[i].load(kp + (int64_t)row * a.ldk + ch * 8);
       vc[i].load(vp + (int64_t)row * a.ldv + ch * 8);
     } else {
@@ -106,7 +114,8 @@ __global__ __launch_bounds__(64 * kCausalWaves) void causal_attn_kernel(CausalAr
   float sv[KB][16];
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
-    if (kb > wave) continue;   // wave-uniform: the blocks above the diagonal are never computed
+    // wave-uniform: the blocks above the diagonal, or past the last key, are never computed
+    if (CAUSAL ? kb > wave : kb * 32 >= L) continue;
     f32x16_t acc = {};
 #pragma unroll
     for (int t = 0; t < NKT; ++t) {
@@ -115,17 +124,23 @@ __global__ __launch_bounds__(64 * kCausalWaves) void causal_attn_kernel(CausalAr
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) sv[kb][r] = acc[r];
-    if (kb == wave) {   // the diagonal block: key 32 kb + j against query 32 kb + qi
+    if (CAUSAL) {
+      if (kb == wave) {   // the diagonal block: key 32 kb + j against query 32 kb + qi
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (acc_row(r, hh) > qi) sv[kb][r] = -INFINITY;
+      }
+    } else if (kb * 32 + 32 > L) {   // the block that holds key L: the zero rows L .. are masked by index
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (acc_row(r, hh) > qi) sv[kb][r] = -INFINITY;
+        if (kb * 32 + acc_row(r, hh) >= L) sv[kb][r] = -INFINITY;
     }
   }
   const float c = a.scale_log2;
   float mx = -INFINITY;
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
-    if (kb > wave) continue;
+    if (CAUSAL ? kb > wave : kb * 32 >= L) continue;
 #pragma unroll
     for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sv[kb][r]);
   }
@@ -134,7 +149,7 @@ __global__ __launch_bounds__(64 * kCausalWaves) void causal_attn_kernel(CausalAr
   float l = 0.f;
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
-    if (kb > wave) continue;
+    if (CAUSAL ? kb > wave : kb * 32 >= L) continue;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       sv[kb][r] = round_p(MP{}, fast_exp2(fmaf(sv[kb][r], c, -mx)));   // a masked key: exp2(-inf) = 0
@@ -147,7 +162,7 @@ __global__ __launch_bounds__(64 * kCausalWaves) void causal_attn_kernel(CausalAr
   for (int dt = 0; dt < NDT; ++dt) O[dt] = f32x16_t{};
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
-    if (kb > wave) continue;
+    if (CAUSAL ? kb > wave : kb * 32 >= L) continue;
     pv_block<VS, NDT>(MP{}, O, Vs, kb * 32, sv[kb], lane);
   }
   // every row attends to key 0 at least, and the row's largest weight is exp2(0) = 1: l >= 1, no
@@ -243,9 +258,10 @@ __global__ __launch_bounds__(64 * kLnRowsPerBlock) void layer_norm_kernel(p2p_la
   }
 }
 
-// out[m, j] = h * sigmoid(1.702 h), h = in[m, j] + bias[j]
-template <bool F16>
-__global__ __launch_bounds__(256) void bias_quick_gelu_kernel(p2p_bias_act_args a, int64_t n_vec) {
+// out[m, j] = act(h), h = in[m, j] + bias[j]; act: h * sigmoid(1.702 h), or (ERF) the exact GELU
+// 0.5 h (1 + erf(h / sqrt 2)) as geglu_kernel (p2p_unet.hip) writes it
+template <bool F16, bool ERF>
+__global__ __launch_bounds__(256) void bias_act_kernel(p2p_bias_act_args a, int64_t n_vec) {
   const int64_t iv = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (iv >= n_vec) return;
   const int dv = a.d >> 3;
@@ -257,7 +273,8 @@ __global__ __launch_bounds__(256) void bias_quick_gelu_kernel(p2p_bias_act_args 
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const float h = ld16<F16>(vi[i]) + ld16<F16>(vb[i]);
-    o[i] = st16<F16>(h / (1.f + __expf(-1.702f * h)));
+    if (ERF) o[i] = st16<F16>(0.5f * h * (1.f + erff(h * 0.70710678118654752f)));
+    else o[i] = st16<F16>(h / (1.f + __expf(-1.702f * h)));
   }
   *reinterpret_cast<u16x8_t*>(static_cast<uint16_t*>(a.out) + m * a.out_row_stride + j) = o;
 }
@@ -267,14 +284,14 @@ bool io16(int dtype) { return dtype == P2P_DTYPE_BF16 || dtype == P2P_DTYPE_F16;
 
 }  // namespace
 
-int run_causal_attn(const CausalArgs& a, int io_dtype, hipStream_t st) {
+int run_text_attn(const TextAttnArgs& a, bool causal, int io_dtype, hipStream_t st) {
   const dim3 grid((unsigned)(a.N * a.H)), block(64 * kCausalWaves);
-  if (io_dtype == P2P_DTYPE_F16)
-    launch_kernel((causal_attn_kernel<f16_t, QkF16, MmaF16>), grid, block, 0, st, a);
-  else if (io_dtype == P2P_DTYPE_BF16)
-    launch_kernel((causal_attn_kernel<uint16_t, QkBf16<uint16_t>, MmaBf16>), grid, block, 0, st, a);
-  else
-    return P2P_E_DTYPE;
+  if (io_dtype != P2P_DTYPE_F16 && io_dtype != P2P_DTYPE_BF16) return P2P_E_DTYPE;
+  const bool f16 = io_dtype == P2P_DTYPE_F16;
+  if (causal && f16) launch_kernel((text_attn_kernel<true, f16_t, QkF16, MmaF16>), grid, block, 0, st, a);
+  else if (causal) launch_kernel((text_attn_kernel<true, uint16_t, QkBf16<uint16_t>, MmaBf16>), grid, block, 0, st, a);
+  else if (f16) launch_kernel((text_attn_kernel<false, f16_t, QkF16, MmaF16>), grid, block, 0, st, a);
+  else launch_kernel((text_attn_kernel<false, uint16_t, QkBf16<uint16_t>, MmaBf16>), grid, block, 0, st, a);
   return (int)hipGetLastError();
 }
 
@@ -293,7 +310,7 @@ int run_layer_norm(const p2p_layer_norm_args& a, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-int run_bias_quick_gelu(const p2p_bias_act_args& a, hipStream_t st) {
+int run_bias_act(const p2p_bias_act_args& a, bool erf, hipStream_t st) {
   if (!a.in || !a.bias || !a.out) return P2P_E_ARG;
   if (a.rows < 1 || a.d < 1 || a.in_row_stride < a.d || a.out_row_stride < a.d) return P2P_E_ARG;
   if (!io16(a.dtype)) return P2P_E_DTYPE;
@@ -302,8 +319,10 @@ int run_bias_quick_gelu(const p2p_bias_act_args& a, hipStream_t st) {
   const int64_t n_vec = (int64_t)a.rows * (a.d / 8);
   if ((n_vec + 255) / 256 > INT32_MAX) return P2P_E_ARG;
   const dim3 grid((unsigned)((n_vec + 255) / 256));
-  if (a.dtype == P2P_DTYPE_F16) launch_kernel(bias_quick_gelu_kernel<true>, grid, dim3(256), 0, st, a, n_vec);
-  else launch_kernel(bias_quick_gelu_kernel<false>, grid, dim3(256), 0, st, a, n_vec);
+  if (erf && a.dtype == P2P_DTYPE_F16) launch_kernel((bias_act_kernel<true, true>), grid, dim3(256), 0, st, a, n_vec);
+  else if (erf) launch_kernel((bias_act_kernel<false, true>), grid, dim3(256), 0, st, a, n_vec);
+  else if (a.dtype == P2P_DTYPE_F16) launch_kernel((bias_act_kernel<true, false>), grid, dim3(256), 0, st, a, n_vec);
+  else launch_kernel((bias_act_kernel<false, false>), grid, dim3(256), 0, st, a, n_vec);
   return (int)hipGetLastError();
 }
 

@@ -203,6 +203,8 @@ def lib():
         L.p2p_causal_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp]
         L.p2p_layer_norm.argtypes = [ctypes.POINTER(LayerNormArgs), vp]
         L.p2p_bias_quick_gelu.argtypes = [ctypes.POINTER(BiasActArgs), vp]
+        L.p2p_text_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp]
+        L.p2p_bias_gelu.argtypes = [ctypes.POINTER(BiasActArgs), vp]
         L.p2p_image_u8.argtypes = [ctypes.POINTER(ImageU8Args), vp]
         L.p2p_image_to_model.argtypes = [ctypes.POINTER(ImageToModelArgs), vp]
         L.p2p_clock_probe.argtypes = [vp, i32, i32, vp]
@@ -234,7 +236,7 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu",
                     "p2p_self_attn_kernel", "p2p_cross_attn_kernel", "p2p_plms_step", "p2p_image_u8",
                     "p2p_image_to_model", "p2p_group_norm_stats_floats", "p2p_causal_attn_fwd", "p2p_layer_norm",
-                    "p2p_bias_quick_gelu")
+                    "p2p_bias_quick_gelu", "p2p_text_attn_fwd", "p2p_bias_gelu")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -772,27 +774,48 @@ def image_to_model(img: torch.Tensor, dtype: torch.dtype):
     return out if ok else None
 
 
-# -- the text encoder (p2p_text.hip).  As the glue above: None where the library reports the dtype,
+# -- the text encoders (p2p_text.hip).  As the glue above: None where the library reports the dtype,
 # shape or alignment unsupported -- or the tensors are not on the GPU -- and the caller runs its
 # torch lines; any other rejection raises.
 LN_MAX_CHANNELS = 2048
 
 
-def causal_attn(q, k, v, heads: int, scale: float):
-    """softmax(causal(q k^T * scale)) v for q / k / v [N, T, heads * 64] with a unit last stride
-    (strided views of one QKV GEMM output are served as they are), T <= MAX_KEYS_CROSS
-    (p2p_causal_attn_fwd).  Returns a dense [N, T, heads * 64] tensor."""
+def _text_attn(q, k, v, heads, scale, key_counts, what):
     if not (q.is_cuda and k.is_cuda and v.is_cuda) or q.dtype not in (torch.bfloat16, torch.float16):
         return None
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     for n0 in range(0, q.shape[0], MAX_BATCH):     # the library takes MAX_BATCH entries per launch
         sl = slice(n0, n0 + MAX_BATCH)
         t = make_tensors(q[sl], k[sl], v[sl], o[sl], heads, scale, "bf16")
-        rc = lib().p2p_causal_attn_fwd(ctypes.byref(t), _stream(q.device))
+        if what == "p2p_causal_attn_fwd":
+            rc = lib().p2p_causal_attn_fwd(ctypes.byref(t), _stream(q.device))
+        else:
+            counts = key_counts[sl].data_ptr() if key_counts is not None else None
+            rc = lib().p2p_text_attn_fwd(ctypes.byref(t), counts, _stream(q.device))
         if rc in (P2P_E_HEAD_DIM, P2P_E_KEYS, P2P_E_DTYPE, P2P_E_ALIGN):
             return None                            # decided from the shapes: the first chunk's answer is every chunk's
-        _check(rc, "p2p_causal_attn_fwd")
+        _check(rc, what)
     return o
+
+
+def causal_attn(q, k, v, heads: int, scale: float):
+    """softmax(causal(q k^T * scale)) v for q / k / v [N, T, heads * 64] with a unit last stride
+    (strided views of one QKV GEMM output are served as they are), T <= MAX_KEYS_CROSS
+    (p2p_causal_attn_fwd).  Returns a dense [N, T, heads * 64] tensor."""
+    return _text_attn(q, k, v, heads, scale, None, "p2p_causal_attn_fwd")
+
+
+def text_attn(q, k, v, heads: int, scale: float, key_counts=None):
+    """softmax(q k^T * scale) v, every token attending to every token, for the operands of
+    causal_attn (p2p_text_attn_fwd).  ``key_counts``: None, or a contiguous int32 [N] tensor on the
+    operands' device: entry n attends to its first key_counts[n] tokens only (the kernel clamps a
+    count into [1, T]); all T rows are computed.  Returns a dense [N, T, heads * 64] tensor."""
+    if key_counts is not None:
+        _require_cuda(key_counts)
+        if (key_counts.dtype != torch.int32 or key_counts.shape != (q.shape[0],) or not key_counts.is_contiguous()
+                or key_counts.device != q.device):
+            raise HipError(f"text_attn: key_counts must be a contiguous int32 [{q.shape[0]}] tensor on {q.device}")
+    return _text_attn(q, k, v, heads, scale, key_counts, "p2p_text_attn_fwd")
 
 
 def layer_norm(x, gamma, beta, eps: float, add=None, add_bias=None, sum_out=None):
@@ -822,6 +845,16 @@ def layer_norm(x, gamma, beta, eps: float, add=None, add_bias=None, sum_out=None
 def bias_quick_gelu(x, bias, out=None):
     """h * sigmoid(1.702 h), h = x + bias, for x [..., D] with a unit last stride (p2p_bias_quick_gelu);
     ``out``: None (a new dense tensor) or x itself (in place)."""
+    return _bias_act(x, bias, out, "p2p_bias_quick_gelu")
+
+
+def bias_gelu(x, bias, out=None):
+    """0.5 h (1 + erf(h / sqrt 2)), h = x + bias: the exact GELU, for the operands of bias_quick_gelu
+    (p2p_bias_gelu)."""
+    return _bias_act(x, bias, out, "p2p_bias_gelu")
+
+
+def _bias_act(x, bias, out, what):
     D = x.shape[-1]
     if not (x.is_cuda and bias.is_cuda) or bias.dtype != x.dtype:
         return None
@@ -829,7 +862,7 @@ def bias_quick_gelu(x, bias, out=None):
     if x2.stride(-1) != 1 or x2.data_ptr() != x.data_ptr():
         return None
     if out is not None and out is not x:
-        raise HipError("bias_quick_gelu: out is None or the input itself")
+        raise HipError(f"{what}: out is None or the input itself")
     res = x if out is x else x.new_empty(x.shape)
     g = BiasActArgs()
     g.inp, g.bias, g.out = x2.data_ptr(), _vec(bias, x, D).data_ptr(), res.data_ptr()
@@ -837,4 +870,4 @@ def bias_quick_gelu(x, bias, out=None):
     g.out_row_stride = g.in_row_stride if out is x else D
     g.rows, g.d = x2.shape[0], D
     g.dtype = _glue_dtype(x)
-    return res if _glue_rc(lib().p2p_bias_quick_gelu(ctypes.byref(g), _stream(x.device)), "p2p_bias_quick_gelu") else None
+    return res if _glue_rc(getattr(lib(), what)(ctypes.byref(g), _stream(x.device)), what) else None

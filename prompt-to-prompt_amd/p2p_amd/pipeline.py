@@ -87,19 +87,45 @@ class SyntheticLatentDiffusion:
     ptp_utils.py:98-126).  The ldm-text2im-large-256 U-Net is the SD topology with a 1280-d
     LDMBert context and a 32x32 latent (diffusers config -- external knowledge, not in the
     container), so every attention layer has P <= 1024 and main.py:131 stores all of them.
-    Random-init weights, seeded embedding-table "LDMBert", DDIM scheduler; no VQ-VAE."""
+    Random-init weights, DDIM scheduler; by default a seeded embedding-table "LDMBert" and no
+    VQ-VAE (text2image_ldm then returns latents).  ``unet_config``: keyword arguments of the U-Net
+    in place of that shape (tests run a narrow one).  ``bert``: build the random-init
+    ``ldm_bert.LDMBertModel`` (or, with ``bert_config``, one of those keyword arguments) in the
+    U-Net's dtype in place of the embedding table, so that every context row depends on every
+    token; its token table covers the stand-in tokenizer's ids (49408 rows, not BERT's 30522).
+    ``vqvae``: build the random-init ``vae.AutoencoderKL`` (latent 4, f8: 32x32 -> 256x256; or, with
+    ``vqvae_config``, one of those keyword arguments) in the U-Net's dtype, so that text2image_ldm
+    returns uint8 images.  Both are built last, each from a generator of its own: the U-Net's
+    weights do not change with them."""
 
-    def __init__(self, device="cuda", dtype=torch.float32, seed=0):
+    def __init__(self, device="cuda", dtype=torch.float32, seed=0, unet_config=None, bert=False, bert_config=None,
+                 vqvae=False, vqvae_config=None):
         self.device = torch.device(device)
         self.tokenizer = default_tokenizer()
         torch.manual_seed(seed)
-        self.unet = UNet2DConditionModel(cross_attention_dim=1280).to(self.device, dtype).eval()
+        self.unet = UNet2DConditionModel(**(unet_config or dict(cross_attention_dim=1280))).to(self.device, dtype).eval()
         for p in self.unet.parameters():
             p.requires_grad_(False)
-        self.bert = SyntheticTextEncoder(dim=1280, seed=2).to(self.device)
+        ldm_bert = bert or bert_config is not None
+        # (the stand-in draws from a generator of its own: leaving it out moves no other weight)
+        self.bert = None if ldm_bert else SyntheticTextEncoder(dim=1280, seed=2).to(self.device)
         self.scheduler = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                                        clip_sample=False, set_alpha_to_one=False)
         self.vqvae = None
+        if ldm_bert:
+            from .ldm_bert import LDMBertModel
+            g = torch.Generator().manual_seed(seed + 1)
+            self.bert = LDMBertModel(**{"vocab_size": VOCAB, **(bert_config or {})}, generator=g)
+            self.bert = self.bert.to(self.device, dtype).eval()
+            for p in self.bert.parameters():
+                p.requires_grad_(False)
+        if vqvae or vqvae_config is not None:
+            from .vae import AutoencoderKL
+            with torch.random.fork_rng(devices=[]):     # nn.Module's default init draws from the global generator
+                torch.manual_seed(seed + 2)
+                self.vqvae = AutoencoderKL(**(vqvae_config or {})).to(self.device, dtype).eval()
+            for p in self.vqvae.parameters():
+                p.requires_grad_(False)
 
 
 LDM_PROMPTS = ["A painting of a squirrel eating a burger", "A painting of a squirrel eating a lasagna"]
