@@ -183,7 +183,8 @@ int p2p_attn_fwd_lse(const p2p_attn_tensors* t, float* lse, p2p_stream_t stream)
 
 /* Backward of O = softmax(Q K^T * scale) V for the same tensors (t->o = the forward's O):
  *   dV = P^T dO,  dS = P o (dO V^T - rowsum(dO o O)),  dQ = scale dS K,  dK = scale dS^T Q.
- * dout and dq use q's layout (strides of t->q / t->o); dk, dv are packed [n_batch, n_key,
+ * dout is read with t->o's row and batch strides, dq is written with t->q's (elements past
+ * n_heads * head_dim of a dq row are left alone); dk, dv are packed [n_batch, n_key,
  * n_heads * head_dim], written (not accumulated) in io_dtype, or in f32 when kv_f32 = 1.
  * delta: workspace [n_batch * n_heads, n_query] f32.  workspace: p2p_attn_bwd_workspace(t)
  * bytes (NULL when that is 0): when the key tiles alone would leave the chip idle (cross

@@ -15,7 +15,13 @@
 // key/value pass splits the queries over workgroups: each split stores its partial dK/dV (f32)
 // into a workspace and bwd_kv_reduce_kernel adds them in split order (deterministic; the f32
 // atomics this replaced serialised on the shared rows: 3-4x slower).
+// f32 tensors: S is recomputed as the forward forms it, split-bf16 (hi = bf16(x), lo = bf16(x - hi),
+// three of the four products: QkSplit, p2p_device.h) -- the lse it is compared with came from that
+// S, and a logit rounded to bf16 inputs is off by ~|c S| 2^-9, which exp turns into the same
+// relative error of every P (4 % of the gradients' norm at |c S| ~ 20).  Everything P and dS
+// multiply (dO, V, K, Q) is still read as bf16: those roundings enter linearly.
 #include <cstdlib>
+#include <type_traits>
 
 #include "p2p_device.h"
 #include "p2p_kernels.h"
@@ -58,9 +64,23 @@ __device__ __forceinline__ short8_t row_frag(const IO* row, int col, bool ok) {
   return *reinterpret_cast<const short8_t*>(t);
 }
 
+// the same 8 elements of an f32 row as the split pair: hi = bf16(x), lo = bf16(x - hi)
+template <int D>
+__device__ __forceinline__ void row_frag_split(const float* row, int col, bool ok, short8_t& hi, short8_t& lo) {
+  hi = lo = short8_t{0, 0, 0, 0, 0, 0, 0, 0};
+  if (!ok || col >= D) return;
+  Chunk8<float> c;
+  c.load(row + col);
+  uint16_t h[8] __attribute__((aligned(16))), l[8] __attribute__((aligned(16)));
+  c.store_split(h, l);
+  hi = *reinterpret_cast<const short8_t*>(h);
+  lo = *reinterpret_cast<const short8_t*>(l);
+}
+
 // Tile staging shared by both passes: `rows` rows of two [*, H*D] tensors (X, Y) into a row
 // image [T][KS] (ds_read_b128 reads) and a transposable image [T][VS] (ds_read_b64_tr_b16),
-// both bf16; rows past `limit` are zeros.
+// both bf16; rows past `limit` are zeros.  f32 tensors: X's row image is the hi plane of its split
+// pair and `xlo` [T][KS] receives the lo plane.
 template <typename IO, int D, int T, int NT>
 struct TileStage {
   static constexpr int DK = (D + 15) / 16 * 16;
@@ -85,14 +105,20 @@ struct TileStage {
       }
     }
   }
-  // images: xrow [T][KS], xtr [T][VS], yrow [T][KS], ytr [T][VS] (any may be null)
-  __device__ __forceinline__ void write(uint16_t* xrow, uint16_t* xtr, uint16_t* yrow, uint16_t* ytr, int tid) {
+  // images: xrow [T][KS], xtr [T][VS], yrow [T][KS], ytr [T][VS] (any may be null), xlo [T][KS]
+  // (f32 tensors only, with xrow)
+  __device__ __forceinline__ void write(uint16_t* xrow, uint16_t* xtr, uint16_t* yrow, uint16_t* ytr, uint16_t* xlo,
+                                        int tid) {
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int c = tid + i * NT;
       if (c < T * CPR) {
         const int r = c / CPR, ch = c - r * CPR;
-        if (xrow) xr[i].store(xrow + r * KS + ch * 8);
+        if constexpr (std::is_same<IO, float>::value) {
+          if (xrow) xr[i].store_split(xrow + r * KS + ch * 8, xlo + r * KS + ch * 8);
+        } else {
+          if (xrow) xr[i].store(xrow + r * KS + ch * 8);
+        }
         if (xtr) xr[i].store(xtr + r * VS + ch * 8);
         if (yrow) yr[i].store(yrow + r * KS + ch * 8);
         if (ytr) yr[i].store(ytr + r * VS + ch * 8);
@@ -109,7 +135,8 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dq_kernel(BwdArgs a) {
   constexpr int NDT = St::DV / 32;
   constexpr int KS = St::KS, VS = St::VS;
   constexpr int NSB = T / 32;
-  constexpr int IMG = T * (2 * KS + VS);          // Krow, Vrow, Ktr per buffer (elements)
+  constexpr bool kSplit = std::is_same<IO, float>::value;   // split-bf16 S (f32 tensors)
+  constexpr int IMG = T * (2 * KS + VS) + (kSplit ? T * KS : 0);   // Krow, Vrow, Ktr (, Klo) per buffer (elements)
   __shared__ __attribute__((aligned(16))) uint16_t smem[2 * IMG];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5, qi = lane & 31;
@@ -128,10 +155,11 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dq_kernel(BwdArgs a) {
 
   for (int i = tid; i < IMG; i += 64 * WAVES) reinterpret_cast<uint32_t*>(smem)[i] = 0u;  // both buffers
 
-  short8_t qf[NKT], gf[NKT];
+  short8_t qf[NKT], gf[NKT], ql[kSplit ? NKT : 1];
 #pragma unroll
   for (int t = 0; t < NKT; ++t) {
-    qf[t] = row_frag<IO, D>(qp + (int64_t)p * a.ldq, 16 * t + 8 * hh, prow);
+    if constexpr (kSplit) row_frag_split<D>(qp + (int64_t)p * a.ldq, 16 * t + 8 * hh, prow, qf[t], ql[t]);
+    else qf[t] = row_frag<IO, D>(qp + (int64_t)p * a.ldq, 16 * t + 8 * hh, prow);
     gf[t] = row_frag<IO, D>(gp + (int64_t)p * a.lddo, 16 * t + 8 * hh, prow);
   }
   const float lse = prow ? a.lse[(int64_t)nh * a.P + p] : INFINITY;
@@ -145,13 +173,14 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dq_kernel(BwdArgs a) {
   const int ntiles = (a.K + T - 1) / T;
   __syncthreads();
   st.load(kp, a.ldk, vp, a.ldv, 0, a.K, tid);
-  st.write(smem, smem + 2 * T * KS, smem + T * KS, nullptr, tid);
+  st.write(smem, smem + 2 * T * KS, smem + T * KS, nullptr, smem + T * (2 * KS + VS), tid);
   __syncthreads();
   for (int kt = 0; kt < ntiles; ++kt) {
     uint16_t* buf = smem + (kt & 1) * IMG;
     const uint16_t* Krow = buf;
     const uint16_t* Vrow = buf + T * KS;
     const uint16_t* Ktr = buf + 2 * T * KS;
+    const uint16_t* Klo = buf + T * (2 * KS + VS);
     if (kt + 1 < ntiles) st.load(kp, a.ldk, vp, a.ldv, (kt + 1) * T, a.K, tid);
 #pragma unroll
     for (int sb = 0; sb < NSB; ++sb) {
@@ -160,6 +189,13 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dq_kernel(BwdArgs a) {
       for (int t = 0; t < NKT; ++t) {
         const short8_t kf = *reinterpret_cast<const short8_t*>(Krow + (sb * 32 + qi) * KS + 16 * t + 8 * hh);
         const short8_t vf = *reinterpret_cast<const short8_t*>(Vrow + (sb * 32 + qi) * KS + 16 * t + 8 * hh);
+        if constexpr (kSplit) {   // lo x hi, hi x lo, then hi x hi below (QkSplit::mma's order)
+          const short8_t kl = *reinterpret_cast<const short8_t*>(Klo + (sb * 32 + qi) * KS + 16 * t + 8 * hh);
+          S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, kl),
+                                                      __builtin_bit_cast(bf16x8_t, qf[t]), S, 0, 0, 0);
+          S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, kf),
+                                                      __builtin_bit_cast(bf16x8_t, ql[t]), S, 0, 0, 0);
+        }
         S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, kf),
                                                     __builtin_bit_cast(bf16x8_t, qf[t]), S, 0, 0, 0);
         dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vf),
@@ -176,7 +212,7 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dq_kernel(BwdArgs a) {
     }
     if (kt + 1 < ntiles) {
       uint16_t* nb = smem + ((kt + 1) & 1) * IMG;
-      st.write(nb, nb + 2 * T * KS, nb + T * KS, nullptr, tid);
+      st.write(nb, nb + 2 * T * KS, nb + T * KS, nullptr, nb + T * (2 * KS + VS), tid);
     }
     __syncthreads();
   }
@@ -205,7 +241,9 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dkv_kernel(BwdArgs a) {
   constexpr int KS = St::KS, VS = St::VS;
   constexpr int NSB = T / 32;
   constexpr bool kDV = WANT & 1, kDK = WANT & 2;
-  constexpr int IMG = T * (2 * KS + 2 * VS) + 2 * T * 2;   // Qrow, dOrow, Qtr, dOtr + lse/delta (f32)
+  constexpr bool kSplit = std::is_same<IO, float>::value;   // split-bf16 S (f32 tensors)
+  constexpr int LO = T * (2 * KS + 2 * VS) + 2 * T * 2;     // where Qlo starts
+  constexpr int IMG = LO + (kSplit ? T * KS : 0);   // Qrow, dOrow, Qtr, dOtr + lse/delta (f32) (, Qlo)
   __shared__ __attribute__((aligned(16))) uint16_t smem[2 * IMG];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5, ki = lane & 31;
@@ -228,10 +266,11 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dkv_kernel(BwdArgs a) {
 
   for (int i = tid; i < IMG; i += 64 * WAVES) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
 
-  short8_t kf[NKT], vf[NKT];
+  short8_t kf[NKT], vf[NKT], kl[kSplit ? NKT : 1];
 #pragma unroll
   for (int t = 0; t < NKT; ++t) {
-    kf[t] = row_frag<IO, D>(kp + (int64_t)key * a.ldk, 16 * t + 8 * hh, krow);
+    if constexpr (kSplit) row_frag_split<D>(kp + (int64_t)key * a.ldk, 16 * t + 8 * hh, krow, kf[t], kl[t]);
+    else kf[t] = row_frag<IO, D>(kp + (int64_t)key * a.ldk, 16 * t + 8 * hh, krow);
     if constexpr (kDK) vf[t] = row_frag<IO, D>(vp + (int64_t)key * a.ldv, 16 * t + 8 * hh, krow);
   }
   f32x16_t dV[kDV ? NDT : 1], dK[kDK ? NDT : 1];
@@ -250,7 +289,7 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dkv_kernel(BwdArgs a) {
   St st;
   auto stage_rows = [&](int qt, uint16_t* b) {
     const int row0 = q_begin + qt * T;
-    st.write(b, b + 2 * T * KS, b + T * KS, b + 2 * T * KS + T * VS, tid);
+    st.write(b, b + 2 * T * KS, b + T * KS, b + 2 * T * KS + T * VS, b + LO, tid);
     float* lb = reinterpret_cast<float*>(b + T * (2 * KS + 2 * VS));
     for (int i = tid; i < T; i += 64 * WAVES) {
       const int q = row0 + i;
@@ -271,6 +310,7 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dkv_kernel(BwdArgs a) {
     const uint16_t* Qtr = buf + 2 * T * KS;
     const uint16_t* Gtr = buf + 2 * T * KS + T * VS;
     const float* lb = reinterpret_cast<const float*>(buf + T * (2 * KS + 2 * VS));
+    const uint16_t* Qlo = buf + LO;
     if (qt + 1 < ntiles) st.load(qp, a.ldq, gp, a.lddo, q_begin + (qt + 1) * T, q_end, tid);
 #pragma unroll
     for (int sb = 0; sb < NSB; ++sb) {
@@ -278,6 +318,13 @@ __global__ __launch_bounds__(64 * WAVES) void bwd_dkv_kernel(BwdArgs a) {
 #pragma unroll
       for (int t = 0; t < NKT; ++t) {
         const short8_t qa = *reinterpret_cast<const short8_t*>(Qrow + (sb * 32 + ki) * KS + 16 * t + 8 * hh);
+        if constexpr (kSplit) {   // lo x hi, hi x lo, then hi x hi below
+          const short8_t qlo = *reinterpret_cast<const short8_t*>(Qlo + (sb * 32 + ki) * KS + 16 * t + 8 * hh);
+          S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, qlo),
+                                                      __builtin_bit_cast(bf16x8_t, kf[t]), S, 0, 0, 0);
+          S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, qa),
+                                                      __builtin_bit_cast(bf16x8_t, kl[t]), S, 0, 0, 0);
+        }
         S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, qa),
                                                     __builtin_bit_cast(bf16x8_t, kf[t]), S, 0, 0, 0);
         if constexpr (kDK) {

@@ -5,11 +5,33 @@ The kernels use bf16 MFMA operands with f32 accumulation, so gradients are check
 their own magnitude: max |grad - ref| <= 3e-2 * max |ref| (bf16 keeps 8 significant bits; dK sums
 bf16-rounded dS over up to 4096 queries), and
 the cosine of every gradient with the reference >= 0.999.
+
+Below that, the pair at the C ABI on the shapes of backward_ref.CASES against the float64
+reference and the bounds of backward_ref (lse 2^-7 absolute; elementwise 8u * B and Frobenius 6u
+for bf16 tensors, 7.2u * B and 9u for f32 tensors, u = 2^-9).  Maxima MEASURED ON THE GPU (MI355X,
+2026-10-20) over the 11 cases, in units of u (case in brackets):
+
+             lse (absolute)   O      delta   dQ     dK     dV
+  bf16 elem  3.40e-3 [7]      3.18   0.78    0.94   1.12   4.06 [9]
+  bf16 frob                   1.18   1.15    3.13   2.93   1.25
+  f32  elem  4.13e-3 [9]      3.08   0.74    0.91   1.05   3.90 [9]
+  f32  frob                   1.19   1.26    4.49   4.29   1.23
+
+kv_f32 = 1 (cases 2, 4, 5): dK elem 0.18 / frob 1.20, dV elem 1.21 / frob 0.87.  The lse + 2^-5
+control on case 7: Frobenius 11.5 / 11.4 / 11.0 u for dQ / dK / dV.  Before the f32 backward
+recomputed S split-bf16 (it rounded Q and K to bf16), the same run gave f32 dV 63.6 u elementwise and
+dQ / dK / dV 21.7 / 22.0 / 21.5 u Frobenius on case 9, outside the project's 3e-2 (15.4 u), as did
+cases 6 and 7.
 """
+import ctypes
+import functools
+
 import pytest
 import torch
 
-from p2p_amd import attention, config
+from p2p_amd import _hip, attention, config
+
+import backward_ref as br
 
 pytestmark = pytest.mark.gpu
 
@@ -77,3 +99,189 @@ def test_patched_forward_is_differentiable(cuda):
         y = blk(x, context=ctx)
     y.square().mean().backward()
     assert ctx.grad is not None and torch.isfinite(ctx.grad).all() and ctx.grad.abs().max() > 0
+
+
+# ---------------------------------------------------------------------------- the pair at the C ABI
+# p2p_attn_fwd_lse / p2p_attn_bwd called directly (the Python wrapper cannot express strides or
+# kv_f32), at the tile and split edges of backward_ref.CASES, against the float64 reference and the
+# bounds of backward_ref (derived there and in DESIGN.md §5; test_backward_bound.py shows on the CPU
+# that they admit a correct kernel and refuse three seeded faults).
+INDICES = list(range(len(br.CASES)))
+DTYPES = [torch.bfloat16, torch.float32]
+_case_id = lambda i: br.CASE_IDS[i]  # noqa: E731
+_dtype_id = lambda t: "f32" if t == torch.float32 else "bf16"  # noqa: E731
+OUTPUTS = ("O", "lse", "delta", "dQ", "dK", "dV")
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_case(index, dtype):
+    """A case's inputs on the device and their float64 reference, computed once and left alone."""
+    inp = br.make_inputs(index, dtype, device="cuda:0")
+    return inp, br.reference(*inp)
+
+
+def _filled(shape, dtype, dev, fill):
+    """A tensor of NaNs (fill = None) or of one repeated 16-bit pattern."""
+    if fill is None:
+        return torch.full(shape, float("nan"), dtype=dtype, device=dev)
+    x = torch.empty(shape, dtype=dtype, device=dev)
+    x.view(torch.int16).fill_(fill)
+    return x
+
+
+def run_pair(q, k, v, dout, heads, scale, o=None, dq=None, kv_f32=False, lse_shift=0.0, ws_fill=None):
+    """Forward with lse, then the backward, every output and the workspace pre-filled with NaN (or
+    the workspace with `ws_fill`).  o / dq: preallocated (strided) views, else contiguous."""
+    L, dev = _hip.lib(), q.device
+    N, P, C = q.shape
+    K = k.shape[1]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    o = _filled(q.shape, q.dtype, dev, None) if o is None else o
+    dq = _filled(q.shape, q.dtype, dev, None) if dq is None else dq
+    lse = _filled((N * heads, P), torch.float32, dev, None)
+    delta = _filled((N * heads, P), torch.float32, dev, None)
+    kv_dtype = torch.float32 if kv_f32 else q.dtype
+    dk = _filled((N, K, C), kv_dtype, dev, None)
+    dv = _filled((N, K, C), kv_dtype, dev, None)
+    t = _hip.make_tensors(q, k, v, o, heads, scale, "bf16")
+    assert L.p2p_attn_fwd_lse(ctypes.byref(t), lse.data_ptr(), stream) == 0
+    need = int(L.p2p_attn_bwd_workspace(ctypes.byref(t)))
+    ws = _filled((need // 4,), torch.float32, dev, ws_fill) if need else None
+    lse_in = lse + lse_shift if lse_shift else lse
+    rc = L.p2p_attn_bwd(ctypes.byref(t), dout.data_ptr(), lse_in.data_ptr(), delta.data_ptr(), dq.data_ptr(),
+                        dk.data_ptr(), dv.data_ptr(), int(kv_f32), ws.data_ptr() if need else None, need, stream)
+    assert rc == 0
+    torch.cuda.synchronize(dev)
+    return {"O": o, "lse": lse, "delta": delta, "dQ": dq, "dK": dk, "dV": dv, "need": need}
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_run(index, dtype):
+    """The plain run of a case (contiguous, kv_f32 = 0), shared by the tests that read it."""
+    inp, _ = gpu_case(index, dtype)
+    return run_pair(*inp)
+
+
+def _bits(x):
+    return x.contiguous().view(torch.int16 if x.element_size() == 2 else torch.int32)
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
+
+
+def _show(tag, figures):
+    print(tag, " ".join("%s=%.3g" % (k, v if k == "lse" else v / br.U) for k, v in figures.items()),
+          "(lse absolute, the rest in units of u = 2^-9)")
+
+
+@pytest.mark.parametrize("index", INDICES, ids=_case_id)
+@pytest.mark.parametrize("dtype", DTYPES, ids=_dtype_id)
+def test_forward_lse(cuda, index, dtype):
+    (q, k, v, dout, H, scale), ref = gpu_case(index, dtype)
+    got = gpu_run(index, dtype)
+    assert got["need"] == br.workspace_bytes(index)
+    figures = br.measure({"O": got["O"], "lse": got["lse"]}, ref)
+    _show("fwd %s %s" % (br.CASE_IDS[index], _dtype_id(dtype)), figures)
+    assert not br.violations(figures, dtype)
+    if br.CASES[index][2] == 1:
+        # one key: lse = c * s to f32 rounding.  S accumulates d products in f32 (<= d 2^-24 of
+        # sum |q_i k_i|); f32 tensors add the split-bf16 residual (x = hi + lo + r, |r| <= 2^-18 |x|,
+        # and the lo * lo product is dropped: 3 * 2^-18); c and c * s round three times (2^-22),
+        # and log2 of a row sum one ulp from 1 adds 2^-22 absolute.
+        d = q.shape[-1] // H
+        qh, kh = br._heads(q.double(), H), br._heads(k.double(), H)
+        c = scale * br.LOG2E
+        s = (qh * kh).sum(-1).reshape(got["lse"].shape)
+        s_abs = (qh * kh).abs().sum(-1).reshape(got["lse"].shape)
+        tol = c * s_abs * (d * 2.0 ** -24 + (3 * 2.0 ** -18 if dtype == torch.float32 else 0.0)) \
+            + 2.0 ** -22 * (1 + (c * s).abs())
+        err = (got["lse"].double() - c * s).abs()
+        print("K = 1: max |lse - c s| = %.3g, max of its tolerance %.3g" % (err.max().item(), tol.max().item()))
+        assert (err <= tol).all()
+
+
+@pytest.mark.parametrize("index", INDICES, ids=_case_id)
+@pytest.mark.parametrize("dtype", DTYPES, ids=_dtype_id)
+def test_backward_bounds(cuda, index, dtype):
+    _, ref = gpu_case(index, dtype)
+    got = gpu_run(index, dtype)
+    # written, not accumulated: every output was NaN before the call (and so was the workspace: an
+    # empty split must have stored its zeros for the reduction to add)
+    for name in OUTPUTS:
+        assert not torch.isnan(got[name]).any(), name
+    figures = br.measure({n: got[n] for n in ("delta", "dQ", "dK", "dV")}, ref)
+    _show("bwd %s %s" % (br.CASE_IDS[index], _dtype_id(dtype)), figures)
+    assert not br.violations(figures, dtype)
+
+
+@pytest.mark.parametrize("index", [1, 3, 4], ids=_case_id)   # via the reduction, direct, two-pass
+def test_backward_kv_f32(cuda, index):
+    inp, ref = gpu_case(index, torch.bfloat16)
+    plain = gpu_run(index, torch.bfloat16)
+    got = run_pair(*inp, kv_f32=True)
+    assert got["dK"].dtype == got["dV"].dtype == torch.float32
+    for name in ("dK", "dV"):
+        assert not torch.isnan(got[name]).any(), name
+    figures = br.measure({n: got[n] for n in ("dK", "dV")}, ref)
+    _show("kv_f32 %s" % br.CASE_IDS[index], figures)
+    assert not br.violations(figures, torch.bfloat16)
+    # the same accumulators, one rounding
+    for name in ("dK", "dV"):
+        assert _same_bits(got[name].bfloat16(), plain[name]), name
+    assert _same_bits(got["dQ"], plain["dQ"]) and _same_bits(got["delta"], plain["delta"])
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=_dtype_id)
+def test_backward_strided(cuda, dtype):
+    """q, k, v as views of one fused [N, P, 3C] buffer, o and dout as views of [N, P, C + 8]
+    buffers, dq into slot 0 of a [N, P, 3C] buffer: the results of the contiguous run bit for bit,
+    and nothing written outside them."""
+    index = 2
+    assert br.CASES[index][:5] == (1, 130, 130, 3, 64)
+    (q, k, v, dout, H, scale), _ = gpu_case(index, dtype)
+    plain = gpu_run(index, dtype)
+    N, P, C = q.shape
+    SENT = 0x5A5B
+    qkv = torch.cat([q, k, v], dim=-1)
+    obuf = _filled((N, P, C + 8), dtype, cuda, SENT)
+    gbuf = _filled((N, P, C + 8), dtype, cuda, SENT)
+    gbuf[..., :C] = dout
+    dqbuf = _filled((N, P, 3 * C), dtype, cuda, SENT)
+    sent = _filled((N, P, 2 * C), dtype, cuda, SENT)
+    pad = _filled((N, P, 8), dtype, cuda, SENT)
+    got = run_pair(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], gbuf[..., :C], H, scale,
+                   o=obuf[..., :C], dq=dqbuf[..., :C])
+    for name in OUTPUTS:
+        assert _same_bits(got[name].contiguous(), plain[name]), name
+    assert _same_bits(dqbuf[..., C:], sent)
+    assert _same_bits(obuf[..., C:], pad) and _same_bits(gbuf[..., C:], pad)
+    assert _same_bits(qkv, torch.cat([q, k, v], dim=-1))
+
+
+@pytest.mark.parametrize("index", [1, 10], ids=_case_id)
+@pytest.mark.parametrize("dtype", DTYPES, ids=_dtype_id)
+def test_backward_is_deterministic(cuda, index, dtype):
+    """No atomics, partials added in split order: the same bits whatever the workspace held."""
+    inp, _ = gpu_case(index, dtype)
+    first = gpu_run(index, dtype)                     # workspace of NaNs
+    assert first["need"] > 0
+    second = run_pair(*inp, ws_fill=0x7149)           # workspace of 1.19e30s
+    for name in OUTPUTS:
+        assert _same_bits(first[name], second[name]), name
+
+
+def test_backward_bounds_reject_a_wrong_lse(cuda):
+    """Negative control: the forward's lse + 2^-5 handed to the backward (a valid call on valid
+    memory) scales every gradient by 2^(-2^-5), a uniform 2.2 % error.  The bounds refuse it; the
+    criterion of test_attention_backward lets it through, which is why it was not enough."""
+    index = 6
+    inp, ref = gpu_case(index, torch.bfloat16)
+    got = run_pair(*inp, lse_shift=2.0 ** -5)
+    figures = br.measure({n: got[n] for n in ("dQ", "dK", "dV")}, ref)
+    _show("wrong lse %s" % br.CASE_IDS[index], figures)
+    bad = br.violations(figures, torch.bfloat16)
+    assert {"frob:dQ", "frob:dK", "frob:dV"} <= set(bad), bad
+    assert br.old_criterion_passes(got, ref)
+    # and the right lse passes both (test_backward_bounds has the bounds)
+    assert br.old_criterion_passes(gpu_run(index, torch.bfloat16), ref)
