@@ -476,6 +476,66 @@ int p2p_text_attn_fwd(const p2p_attn_tensors* t, const int32_t* key_counts, p2p_
  * p2p_bias_quick_gelu. */
 int p2p_bias_gelu(const p2p_bias_act_args* a, p2p_stream_t stream);
 
+/* The attention-map figures (main.py:293-350; p2p_amd/controllers.py aggregate_attention_device,
+ * cross_attention_panels, show_self_attention_comp), additive to ABI 16. */
+
+#define P2P_MAX_AGG_LAYERS 16
+
+/* aggregate_attention (main.py:293-307) for one prompt, straight from AttentionStore's running
+ * sums: out[p, k] = (sum over layers l, heads h of stores[l][select * heads[l] + h, p, k] / steps)
+ * / (number of terms).  The arithmetic is fixed: every term is an IEEE f32 division by
+ * (float)steps, the terms are added in f32 one after another, layer-major and head-minor (the order
+ * main.py:305 concatenates them), and the sum is divided once by the term count.  Only the
+ * selected prompt's slabs are read.  Four-element vector accesses: P * K % 4 != 0, or a store or
+ * out off 16 bytes, is P2P_E_ALIGN.  n_layers outside [1, P2P_MAX_AGG_LAYERS], select outside
+ * [0, n_prompts), steps < 1, a heads[l] < 1 or a null pointer is P2P_E_ARG. */
+typedef struct {
+  const float* stores[P2P_MAX_AGG_LAYERS]; /* [n_prompts * heads[l], P, K] f32, dense, prompt-major */
+  int32_t heads[P2P_MAX_AGG_LAYERS];
+  int32_t n_layers, n_prompts, select;
+  int32_t P, K;
+  int32_t steps;                           /* AttentionStore.cur_step */
+  float* out;                              /* [P, K] */
+} p2p_maps_aggregate_args;
+
+int p2p_maps_aggregate(const p2p_maps_aggregate_args* a, p2p_stream_t stream);
+
+/* n maps of res x res f32 values as n grey RGB uint8 panels of S x S pixels, normalised and
+ * upscaled as the reference's NumPy + PIL lines do it (main.py:320-324, :342-348), byte for byte.
+ * Element (panel i, pixel p) is in[i * panel_stride + p * pixel_stride] (strides in elements): the
+ * columns of a cross map [res^2, K] are panel_stride 1, pixel_stride K; rows [n, res^2] are
+ * panel_stride res^2, pixel_stride 1.  Pixel (y, x) of panel i goes to the three bytes at
+ * out + i * out_panel_stride + y * out_row_stride + 3 x (strides in bytes), so a row of panels can
+ * be written straight into a wider canvas.
+ *   P2P_PANEL_MAX:    y = (255 * x) / max x, truncated to uint8        (show_cross_attention)
+ *   P2P_PANEL_MINMAX: x' = x - min x, y = (255 * x') / max x', truncated (show_self_attention_comp)
+ * every operation rounded to f32 on its own.  A panel whose divisor is 0, or that holds a NaN,
+ * comes out all zero (the reference's result there is undefined).
+ * The resize is PIL's 8-bit bicubic (a = -0.5): per output pixel P2P_RESIZE_TAPS taps, normalised
+ * and rounded to 22-bit fixed point, the accumulator starting at 2^21, shifted and clamped; the
+ * horizontal pass is rounded to uint8 before the vertical one.  coeffs / bounds: the tap table
+ * int32 [S][P2P_RESIZE_TAPS] and {first input pixel, tap count} int32 [S][2] of a res -> S resize,
+ * built on the host (p2p_amd/_hip.py resize_coeffs); entries that point past the panel are clamped.
+ * 1 <= res <= P2P_PANEL_MAX_RES, res <= S <= P2P_PANEL_MAX_SIDE, S % 4 == 0 (at these sizes no
+ * output pixel has more taps), out_row_stride >= 3 S, a known mode, n >= 1 and no null pointer:
+ * else P2P_E_ARG.  in / coeffs / bounds / out and both byte strides on 4 bytes: else P2P_E_ALIGN. */
+#define P2P_RESIZE_TAPS 5
+#define P2P_PANEL_MAX_RES 64
+#define P2P_PANEL_MAX_SIDE 512
+enum { P2P_PANEL_MAX = 0, P2P_PANEL_MINMAX = 1 };
+
+typedef struct {
+  const float* in;
+  int64_t panel_stride, pixel_stride;      /* elements */
+  const int32_t* coeffs;                   /* [S][P2P_RESIZE_TAPS] */
+  const int32_t* bounds;                   /* [S][2] */
+  uint8_t* out;
+  int64_t out_row_stride, out_panel_stride; /* bytes */
+  int32_t res, n, S, mode;
+} p2p_map_panels_args;
+
+int p2p_map_panels(const p2p_map_panels_args* a, p2p_stream_t stream);
+
 /* Measurement only (ABI 15; bench.py's roofline clock, not part of the reference's interface):
  * n_workgroups one-wave workgroups each read the shader-cycle counter and the constant 100 MHz
  * counter, spin until `ticks` (1..1e6) of the 100 MHz counter have passed, and read both again:

@@ -195,6 +195,9 @@ int run_text_attn(const TextAttnArgs& a, bool causal, int io_dtype, hipStream_t 
 // every argument check happens in these, before the launch
 int run_layer_norm(const p2p_layer_norm_args& a, hipStream_t st);
 int run_bias_act(const p2p_bias_act_args& a, bool erf, hipStream_t st);   // quick-GELU, or the erf GELU
+// the attention-map figures (p2p_viz.hip): every argument check happens in these, before the launch
+int run_maps_aggregate(const p2p_maps_aggregate_args& a, hipStream_t st);
+int run_map_panels(const p2p_map_panels_args& a, hipStream_t st);
 int run_clock_probe(unsigned long long* out, int n_wg, int ticks, hipStream_t st);
 
 }  // namespace p2p

@@ -6,7 +6,8 @@ Host side (Python / PyTorch-ROCm) of the library; the kernels live in ``libp2p_h
 * ``ptp_utils``    -- register_attention_control, sampling loop, word/time tables
 * ``seq_aligner``  -- token alignment and mapper tables
 * ``controllers``  -- main.py's AttentionControl / Store / Edit / Replace / Refine / Reweight /
-                      LocalBlend / get_equalizer / aggregate_attention
+                      LocalBlend / get_equalizer / aggregate_attention / show_cross_attention /
+                      show_self_attention_comp
 * ``null_text``    -- null_text.py's flavour of the same
 * ``programs``     -- device edit programs (cross-attention edits as data)
 * ``unet`` / ``ddim`` / ``pipeline`` -- the SD-v1.4-shaped caller around the hot path

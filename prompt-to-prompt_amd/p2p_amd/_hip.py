@@ -164,6 +164,30 @@ class ImageToModelArgs(ctypes.Structure):
     ]
 
 
+MAX_AGG_LAYERS = 16
+RESIZE_TAPS = 5
+PANEL_MAX_RES = 64
+PANEL_MAX_SIDE = 512
+PANEL_MAX, PANEL_MINMAX = 0, 1
+
+
+class MapsAggregateArgs(ctypes.Structure):
+    _fields_ = [
+        ("stores", ctypes.c_void_p * MAX_AGG_LAYERS), ("heads", ctypes.c_int32 * MAX_AGG_LAYERS),
+        ("n_layers", ctypes.c_int32), ("n_prompts", ctypes.c_int32), ("select", ctypes.c_int32),
+        ("P", ctypes.c_int32), ("K", ctypes.c_int32), ("steps", ctypes.c_int32), ("out", ctypes.c_void_p),
+    ]
+
+
+class MapPanelsArgs(ctypes.Structure):
+    _fields_ = [
+        ("inp", ctypes.c_void_p), ("panel_stride", ctypes.c_int64), ("pixel_stride", ctypes.c_int64),
+        ("coeffs", ctypes.c_void_p), ("bounds", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("out_row_stride", ctypes.c_int64), ("out_panel_stride", ctypes.c_int64),
+        ("res", ctypes.c_int32), ("n", ctypes.c_int32), ("S", ctypes.c_int32), ("mode", ctypes.c_int32),
+    ]
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -207,6 +231,8 @@ def lib():
         L.p2p_bias_gelu.argtypes = [ctypes.POINTER(BiasActArgs), vp]
         L.p2p_image_u8.argtypes = [ctypes.POINTER(ImageU8Args), vp]
         L.p2p_image_to_model.argtypes = [ctypes.POINTER(ImageToModelArgs), vp]
+        L.p2p_maps_aggregate.argtypes = [ctypes.POINTER(MapsAggregateArgs), vp]
+        L.p2p_map_panels.argtypes = [ctypes.POINTER(MapPanelsArgs), vp]
         L.p2p_clock_probe.argtypes = [vp, i32, i32, vp]
         L.p2p_set_launch_events.argtypes = [vp, vp]
         if L.p2p_abi_version() != ABI_VERSION:
@@ -236,7 +262,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_set_launch_events", "p2p_group_norm", "p2p_bias_residual", "p2p_geglu",
                     "p2p_self_attn_kernel", "p2p_cross_attn_kernel", "p2p_plms_step", "p2p_image_u8",
                     "p2p_image_to_model", "p2p_group_norm_stats_floats", "p2p_causal_attn_fwd", "p2p_layer_norm",
-                    "p2p_bias_quick_gelu", "p2p_text_attn_fwd", "p2p_bias_gelu")
+                    "p2p_bias_quick_gelu", "p2p_text_attn_fwd", "p2p_bias_gelu", "p2p_maps_aggregate",
+                    "p2p_map_panels")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -772,6 +799,131 @@ def image_to_model(img: torch.Tensor, dtype: torch.dtype):
     a.n, a.height, a.width, a.dtype = N, H, W, _dtype_code(out)
     ok = _glue_rc(lib().p2p_image_to_model(ctypes.byref(a), _stream(img.device)), "p2p_image_to_model")
     return out if ok else None
+
+
+# -- the attention-map figures (p2p_viz.hip).  None where the kernels do not serve the tensors (not
+# on the GPU, not f32 and dense, P * K % 4 != 0, more than MAX_AGG_LAYERS layers, a panel size
+# outside the supported range): the callers in controllers.py then run their torch / PIL lines.
+def maps_aggregate(stores: Sequence[torch.Tensor], n_prompts: int, select: int, steps: int):
+    """The ``select`` prompt's average over ``stores`` (running sums [n_prompts * heads_l, P, K]) and
+    their heads of sum / steps, [P, K] f32 (p2p_maps_aggregate): main.py:293-307 for one prompt
+    without a scaled copy of any store."""
+    stores = list(stores)
+    if not stores or not all(s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and s.dim() == 3
+                             for s in stores):
+        return None
+    if len(stores) > MAX_AGG_LAYERS:
+        return None
+    P, K = stores[0].shape[1], stores[0].shape[2]
+    if any(s.shape[1:] != (P, K) or s.shape[0] % n_prompts or s.device != stores[0].device for s in stores):
+        raise HipError(f"maps_aggregate: stores must be [{n_prompts} * heads, {P}, {K}] on one device")
+    a = MapsAggregateArgs()
+    for i, s in enumerate(stores):
+        a.stores[i], a.heads[i] = s.data_ptr(), s.shape[0] // n_prompts
+    a.n_layers, a.n_prompts, a.select = len(stores), int(n_prompts), int(select)
+    a.P, a.K, a.steps = P, K, int(steps)
+    out = torch.empty((P, K), dtype=torch.float32, device=stores[0].device)
+    a.out = out.data_ptr()
+    ok = _glue_rc(lib().p2p_maps_aggregate(ctypes.byref(a), _stream(out.device)), "p2p_maps_aggregate")
+    return out if ok else None
+
+
+def _bicubic(x: float) -> float:
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def resize_coeffs(n_in: int, n_out: int):
+    """The tables of PIL's 8-bit bicubic resize of n_in pixels to n_out (Resample.c precompute_coeffs
+    and normalize_coeffs_8bpc, in its operation order, in double precision): (coeffs int32
+    [n_out, ksize], bounds int32 [n_out, 2]).  Output pixel i is
+    clamp((2^21 + sum_t in[bounds[i, 0] + t] * coeffs[i, t]) >> 22, 0, 255), t < bounds[i, 1];
+    ksize is 5 whenever n_in <= n_out."""
+    import math
+    import numpy as np
+    scale = float(n_in) / n_out
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    coeffs = np.zeros((n_out, ksize), dtype=np.int32)
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    ss = 1.0 / filterscale
+    for xx in range(n_out):
+        center = 0.0 + (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n_in) - xmin
+        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x, v in enumerate(w):
+            if ww != 0.0:
+                v = v / ww
+            coeffs[xx, x] = int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22))
+        bounds[xx] = xmin, xmax
+    return coeffs, bounds
+
+
+_resize_tables = {}
+
+
+def _device_resize_tables(res: int, S: int, device):
+    """resize_coeffs(res, S) on ``device``, uploaded once per (res, S, device)."""
+    key = (res, S, str(device))
+    hit = _resize_tables.get(key)
+    if hit is None:
+        coeffs, bounds = resize_coeffs(res, S)
+        assert coeffs.shape == (S, RESIZE_TAPS) and int((bounds[:, 0] + bounds[:, 1]).max()) <= res
+        hit = _resize_tables[key] = (torch.from_numpy(coeffs).to(device), torch.from_numpy(bounds).to(device))
+    return hit
+
+
+def map_panels_supported(res: int, S: int) -> bool:
+    return 1 <= res <= PANEL_MAX_RES and res <= S <= PANEL_MAX_SIDE and S % 4 == 0
+
+
+def map_panels(src: torch.Tensor, n: int, res: int, S: int, mode: int, panel_stride: int, pixel_stride: int,
+               out: Optional[torch.Tensor] = None, out_row_stride: Optional[int] = None,
+               out_panel_stride: Optional[int] = None):
+    """``n`` maps of res x res values of the f32 tensor ``src`` -- element (panel i, pixel p) at flat
+    index i * panel_stride + p * pixel_stride -- as grey RGB uint8 panels of S x S pixels
+    (p2p_map_panels): mode PANEL_MAX is (255 * x / x.max()).astype(uint8), PANEL_MINMAX subtracts the
+    minimum first; the upscale is Image.resize((S, S)), byte for byte.  ``out``: None (a new uint8
+    [n, S, S, 3]) or a dense uint8 canvas on src's device that panel i is written into from byte
+    i * out_panel_stride on, its rows out_row_stride bytes apart; every other byte of it is left
+    alone.  Returns ``out``."""
+    if not (src.is_cuda and src.dtype == torch.float32 and src.is_contiguous()) or not map_panels_supported(res, S):
+        return None
+    if n < 1 or panel_stride < 0 or pixel_stride < 1 or \
+            (n - 1) * panel_stride + (res * res - 1) * pixel_stride >= src.numel():
+        raise HipError(f"map_panels: {n} panels of {res}^2 pixels (strides {panel_stride}, {pixel_stride}) "
+                       f"do not lie in {src.numel()} elements")
+    if mode not in (PANEL_MAX, PANEL_MINMAX):
+        raise HipError(f"map_panels: unknown mode {mode}")
+    if out is None:
+        out = torch.empty((n, S, S, 3), dtype=torch.uint8, device=src.device)
+        out_row_stride, out_panel_stride = 3 * S, 3 * S * S
+    else:
+        _require_cuda(out)
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != src.device:
+            raise HipError("map_panels: out must be a dense uint8 tensor on the maps' device")
+        if out_row_stride < 3 * S or out_panel_stride < 0 or \
+                (n - 1) * out_panel_stride + (S - 1) * out_row_stride + 3 * S > out.numel():
+            raise HipError(f"map_panels: {n} panels (strides {out_row_stride}, {out_panel_stride} bytes) do not "
+                           f"lie in a canvas of {out.numel()} bytes")
+    coeffs, bounds = _device_resize_tables(res, S, src.device)
+    a = MapPanelsArgs()
+    a.inp, a.panel_stride, a.pixel_stride = src.data_ptr(), int(panel_stride), int(pixel_stride)
+    a.coeffs, a.bounds, a.out = coeffs.data_ptr(), bounds.data_ptr(), out.data_ptr()
+    a.out_row_stride, a.out_panel_stride = int(out_row_stride), int(out_panel_stride)
+    a.res, a.n, a.S, a.mode = int(res), int(n), int(S), int(mode)
+    return out if _glue_rc(lib().p2p_map_panels(ctypes.byref(a), _stream(src.device)), "p2p_map_panels") else None
 
 
 # -- the text encoders (p2p_text.hip).  As the glue above: None where the library reports the dtype,

@@ -878,3 +878,126 @@ def reduce_maps(attention_store: AttentionStore, res: int, from_where: List[str]
         raise ValueError(f"no stored {'cross' if is_cross else 'self'} maps at {res}x{res} in {from_where}")
     out = torch.cat(picked, dim=1)
     return out.sum(1) / out.shape[1]
+
+
+# ============================================================================ the figures
+def _picked_stores(attention_store: AttentionStore, res: int, from_where, is_cross: bool):
+    """The running sums aggregate_attention would pick, in its order."""
+    kind = "cross" if is_cross else "self"
+    picked = []
+    for location in from_where:
+        for item in attention_store.attention_store.get(f"{location}_{kind}", ()):
+            if item.shape[1] == res ** 2:
+                picked.append(item)
+    if not picked:
+        why = " (the controller has store_self_maps = False)" if not (is_cross or attention_store.store_self_maps) else ""
+        raise ValueError(f"no stored {kind} maps at {res}x{res} in {tuple(from_where)}{why}")
+    return picked
+
+
+def aggregate_attention_device(attention_store: AttentionStore, res: int, from_where: List[str], is_cross: bool,
+                               select: int, prompts: Optional[List[str]] = None) -> torch.Tensor:
+    """aggregate_attention (main.py:293-307) left on the stores' device, [res, res, K].  Stores that
+    are f32, dense and on the GPU are read by one kernel (p2p_maps_aggregate): only the selected
+    prompt's slabs, each term sum / cur_step, added in aggregate_attention's order -- no scaled copy
+    of every stored map is made.  Anything else runs the torch lines on the picked maps."""
+    n_prompts = len(prompts) if prompts is not None else getattr(attention_store, "batch_size", None)
+    if n_prompts is None:
+        raise ValueError(f"{type(attention_store).__name__} does not know its prompt count: pass prompts=")
+    if not 0 <= select < n_prompts:
+        raise IndexError(f"select {select} outside the {n_prompts} prompts")
+    picked = _picked_stores(attention_store, res, from_where, is_cross)
+    steps = attention_store.cur_step
+    if steps >= 1:
+        out = _hip.maps_aggregate(picked, n_prompts, select, steps)
+        if out is not None:
+            return out.reshape(res, res, out.shape[-1])
+
+    def avg(item):     # get_average_attention's, on the picked maps only
+        if item.is_cuda and item.dtype == torch.float32 and item.is_contiguous():
+            return _hip.store_scale(item, float(steps))
+        return item / steps
+    out = torch.cat([avg(item).reshape(n_prompts, -1, res, res, item.shape[-1])[select] for item in picked], dim=0)
+    return out.sum(0) / out.shape[0]
+
+
+def _panel_expression(x: np.ndarray, size: int, minmax: bool) -> np.ndarray:
+    """One map [res, res] as the reference draws it (main.py:320-324, :342-348), on the host."""
+    from PIL import Image
+    x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    if minmax:
+        x = x - x.min()
+    m = x.max()
+    if bool(torch.isnan(x).any()) or float(m) == 0.0 or bool(torch.isnan(m)):
+        return np.zeros((size, size, 3), dtype=np.uint8)      # as the kernel: the reference's result is undefined
+    grey = (255 * x / m).unsqueeze(-1).expand(*x.shape, 3).numpy().astype(np.uint8)
+    return np.array(Image.fromarray(grey).resize((size, size)))
+
+
+def cross_attention_panels(attention_store: AttentionStore, res: int, from_where: List[str], select: int = 0,
+                           prompts: Optional[List[str]] = None, tokenizer=None, size: int = 256) -> np.ndarray:
+    """The panels of show_cross_attention before their captions: for every token of
+    ``prompts[select]``, its aggregated cross map as 255 * map / map.max(), grey RGB uint8, resized
+    to ``size`` (main.py:314-324), [n_tokens, size, size, 3].  On the GPU one kernel renders all of
+    them from the device aggregate (p2p_map_panels), byte for byte the NumPy + PIL result."""
+    if prompts is None:
+        raise ValueError("cross_attention_panels reads the tokens of prompts[select]: pass prompts=")
+    tokenizer = tokenizer or get_tokenizer()
+    n_tokens = len(tokenizer.encode(prompts[select]))
+    maps = aggregate_attention_device(attention_store, res, from_where, True, select, prompts)
+    K = maps.shape[-1]
+    n_tokens = min(n_tokens, K)
+    if maps.is_cuda:
+        out = _hip.map_panels(maps.contiguous(), n_tokens, res, size, _hip.PANEL_MAX, 1, K)
+        if out is not None:
+            return out.cpu().numpy()
+    maps = maps.float().cpu().numpy()
+    return np.stack([_panel_expression(maps[:, :, i], size, False) for i in range(n_tokens)], axis=0)
+
+
+def show_cross_attention(attention_store: AttentionStore, res: int, from_where: List[str], select: int = 0,
+                         prompts: Optional[List[str]] = None, tokenizer=None):
+    """main.py:310-327: the per-token cross-attention strip, each panel with its token's text under
+    it.  Returns the PIL image (ptp_utils.view_images shows it in a notebook)."""
+    from . import ptp_utils
+    tokenizer = tokenizer or get_tokenizer()
+    panels = cross_attention_panels(attention_store, res, from_where, select, prompts, tokenizer)
+    tokens = tokenizer.encode(prompts[select])
+    images = [ptp_utils.text_under_image(panel, tokenizer.decode([int(tokens[i])])) for i, panel in enumerate(panels)]
+    return ptp_utils.view_images(np.stack(images, axis=0))
+
+
+def self_attention_components(attention_store: AttentionStore, res: int, from_where: List[str], max_com: int = 10,
+                              select: int = 0, prompts: Optional[List[str]] = None) -> np.ndarray:
+    """The first ``max_com`` right singular vectors of the aggregated self-attention map
+    [res^2, res^2] with every row centred by its mean (main.py:335-339), f32 [max_com, res^2].  The
+    aggregate is made on the device; the SVD runs on the host (np.linalg.svd), as the reference's."""
+    maps = aggregate_attention_device(attention_store, res, from_where, False, select, prompts)
+    maps = maps.float().cpu().numpy().reshape((res ** 2, res ** 2))
+    u, s, vh = np.linalg.svd(maps - np.mean(maps, axis=1, keepdims=True))
+    return vh[:max_com]
+
+
+def show_self_attention_comp(attention_store: AttentionStore, res: int, from_where: List[str], max_com: int = 10,
+                             select: int = 0, prompts: Optional[List[str]] = None, size: int = 256):
+    """main.py:330-350: the leading components of the self-attention map side by side, each as
+    255 * (v - v.min()) / (v - v.min()).max(), grey RGB uint8, resized to ``size``.  With the stores
+    on the GPU the strip [size, size * n, 3] is written by one kernel (p2p_map_panels, through its
+    output strides).  Returns the PIL image.  Raises ValueError where no self map at ``res`` is
+    stored (store_self_maps = False, or no such layer)."""
+    from . import ptp_utils
+    picked = _picked_stores(attention_store, res, from_where, False)
+    vh = self_attention_components(attention_store, res, from_where, max_com, select, prompts)
+    n = vh.shape[0]
+    strip = None
+    if picked[0].is_cuda:
+        dev = picked[0].device
+        canvas = torch.empty((size, size * n, 3), dtype=torch.uint8, device=dev)
+        rows = torch.from_numpy(np.ascontiguousarray(vh, dtype=np.float32)).to(dev)
+        out = _hip.map_panels(rows, n, res, size, _hip.PANEL_MINMAX, res * res, 1, out=canvas,
+                              out_row_stride=3 * size * n, out_panel_stride=3 * size)
+        if out is not None:
+            strip = out.cpu().numpy()
+    if strip is None:
+        strip = np.concatenate([_panel_expression(vh[i].reshape(res, res), size, True) for i in range(n)], axis=1)
+    return ptp_utils.view_images(strip)

@@ -21,6 +21,8 @@ import torch
 from . import controllers as _c
 from .attention import materialized_attention, plain_attention
 from .controllers import aggregate_attention, get_tokenizer, default_device, NotFusable  # noqa: F401
+from .controllers import (aggregate_attention_device, cross_attention_panels, self_attention_components,  # noqa: F401
+                          show_cross_attention, show_self_attention_comp)
 from .ptp_words import get_word_inds
 
 NUM_DDIM_STEPS = 50     # null_text.py:23

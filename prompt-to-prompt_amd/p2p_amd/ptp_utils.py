@@ -11,13 +11,81 @@ reference-style controller, to the materialised protocol (attention.py).
 from __future__ import annotations
 
 import os
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from .attention import materialized_attention, plain_attention
 from .ptp_words import get_time_words_attention_alpha, get_word_inds, update_alpha_time_word  # noqa: F401
+
+
+# ------------------------------------------------------------------ figures
+def text_under_image(image: np.ndarray, text: str, text_color: Tuple[int, int, int] = (0, 0, 0)):
+    """ptp_utils.py:24-34: ``image`` [h, w, c] on a white canvas with a band of int(0.2 h) rows under
+    it that carries ``text``.  With cv2 the text is drawn as the reference draws it (Hershey simplex,
+    scale 1, thickness 2); without it, centred in the band in PIL's default font."""
+    h, w, c = image.shape
+    offset = int(h * .2)
+    img = np.ones((h + offset, w, c), dtype=np.uint8) * 255
+    img[:h] = image
+    try:
+        import cv2
+    except ImportError:
+        cv2 = None
+    if cv2 is not None:
+        font = cv2.FONT_HERSHEY_SIMPLEX
+        textsize = cv2.getTextSize(text, font, 1, 2)[0]
+        text_x, text_y = (w - textsize[0]) // 2, h + offset - textsize[1] // 2
+        cv2.putText(img, text, (text_x, text_y), font, 1, text_color, 2)
+        return img
+    from PIL import Image, ImageDraw, ImageFont
+    band = Image.fromarray(np.ascontiguousarray(img[h:]))
+    draw = ImageDraw.Draw(band)
+    font = ImageFont.load_default()
+    left, top, right, bottom = draw.textbbox((0, 0), text, font=font)
+    pos = ((w - (right - left)) // 2 - left, (offset - (bottom - top)) // 2 - top)
+    draw.text(pos, text, fill=tuple(text_color)[:c] if c > 1 else text_color[0], font=font)
+    img[h:] = np.asarray(band).reshape(offset, w, c)
+    return img
+
+
+def view_images(images, num_rows=1, offset_ratio=0.02):
+    """ptp_utils.py:37-62: the images (a list, an array [n, h, w, 3] or one image) as one white grid
+    of ``num_rows`` rows, int(h * offset_ratio) pixels apart, with the reference's padding rule
+    (len % num_rows white cells are appended).  Returns the PIL image; it is displayed only where
+    IPython is installed (a notebook), and never through ``Image.show()``."""
+    from PIL import Image
+    if type(images) is list:
+        num_empty = len(images) % num_rows
+    elif images.ndim == 4:
+        num_empty = images.shape[0] % num_rows
+    else:
+        images = [images]
+        num_empty = 0
+
+    empty_images = np.ones(images[0].shape, dtype=np.uint8) * 255
+    images = [image.astype(np.uint8) for image in images] + [empty_images] * num_empty
+    num_items = len(images)
+
+    h, w, c = images[0].shape
+    offset = int(h * offset_ratio)
+    num_cols = num_items // num_rows
+    image_ = np.ones((h * num_rows + offset * (num_rows - 1),
+                      w * num_cols + offset * (num_cols - 1), 3), dtype=np.uint8) * 255
+    for i in range(num_rows):
+        for j in range(num_cols):
+            image_[i * (h + offset): i * (h + offset) + h:, j * (w + offset): j * (w + offset) + w] = images[
+                i * num_cols + j]
+
+    pil_img = Image.fromarray(image_)
+    try:
+        from IPython.display import display
+    except ImportError:
+        display = None
+    if display is not None:
+        display(pil_img)
+    return pil_img
 
 
 # ------------------------------------------------------------------ sampling loop
