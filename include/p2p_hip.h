@@ -69,7 +69,25 @@ typedef void* p2p_stream_t; /* a hipStream_t */
 
 /* One attention call: q [n_batch, n_query, *], k/v [n_batch, n_key, *], o like q.
  * Strides are in elements.  scale is CrossAttention.scale (head_dim ** -0.5,
- * ptp_utils.py:195). */
+ * ptp_utils.py:195).
+ *
+ * Operand layout contract.  An operand is a view: element (n, row, c) is at
+ * base + n * batch_stride + row * row_stride + c, c < n_heads * head_dim, unit last stride -- so
+ * q, k, v may be column slices of one fused projection ([n, tokens, 3C] / [n, n_key, 2C]: row
+ * stride 3C / 2C, bases C apart), padded rows, or one entry broadcast (batch stride 0).  For every
+ * operand the call needs (a call that takes no v or no q ignores its strides but for alignment):
+ *   - pointers and strides are multiples of 16 bytes, else P2P_E_ALIGN;
+ *   - row stride >= n_heads * head_dim (rows do not overlap; no negative strides);
+ *   - batch stride >= 0; 0 is legal on q, k, v;
+ *   - for o with n_batch > 1, batch stride >= (n_query - 1) * o_row_stride + n_heads * head_dim
+ *     (entries do not overlap: every element of o has one writer);
+ *   - the span ((rows - 1) * row_stride + n_heads * head_dim) * element size <= INT32_MAX, rows =
+ *     n_query for q and o, n_key for k and v (the kernels index inside an entry with 32-bit byte
+ *     offsets);
+ * else P2P_E_ARG, before anything is launched (checked after the call's other arguments).  The
+ * kernels read nothing they use, and write nothing at all, outside the elements of the views:
+ * row padding, the slack between entries and the columns of a fused projection that belong to
+ * another operand keep their bits (tests/test_gpu_layouts.py). */
 typedef struct {
   const void* q;
   const void* k;

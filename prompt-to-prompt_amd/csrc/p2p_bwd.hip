@@ -460,10 +460,9 @@ static int launch_bwd_d(BwdArgs a, hipStream_t st) {
 template <typename IO>
 static int dispatch_bwd(const BwdArgs& a, int d, hipStream_t st) {
   switch (d) {
-    case 40: return launch_bwd_d<IO, 40>(a, st);
-    case 64: return launch_bwd_d<IO, 64>(a, st);
-    case 80: return launch_bwd_d<IO, 80>(a, st);
-    case 160: return launch_bwd_d<IO, 160>(a, st);
+#define P2P_CASE(DD) case DD: return launch_bwd_d<IO, DD>(a, st);
+    P2P_FOR_EACH_BWD_D(P2P_CASE)
+#undef P2P_CASE
     default: return P2P_E_HEAD_DIM;
   }
 }

@@ -34,6 +34,37 @@ int check_tensors(const p2p_attn_tensors* t, bool need_q, bool need_k, bool need
   return 0;
 }
 
+// The operand layout contract (include/p2p_hip.h), for the operands the call needs: the last check
+// of every attention entry point, after check_tensors and the call's own argument checks.
+//   - a row holds its n_heads * head_dim elements: a smaller row stride makes rows overlap (for o, a
+//     write race); a negative one is smaller still;
+//   - batch strides are >= 0 (0 on q / k / v: one entry broadcast to the batch);
+//   - o's batch entries do not overlap;
+//   - the operand's span fits a 32-bit byte offset.  The kernels index inside one batch entry with
+//     32-bit byte offsets into buffer resources whose range make_rsrc clamps to 0x7fffffff:
+//     cross_group_kernel's Q, K and V (Q by the absolute query row, p2p_cross.hip),
+//     cross_attn_kernel's (p2p_cross_entry.hip), self40_kernel's (p2p_self40.hip), and the K / V
+//     tiles of self_attn_fused_kernel, self_attn_multi_kernel and self_wide_kernel -- a larger
+//     operand would wrap or read zeros past the clamp instead of failing.  (The largest span the
+//     product has is 12 MB: P = 4096 rows of a [*, 4096, 1536] 16-bit projection.)
+int check_layout(const p2p_attn_tensors* t, bool need_q, bool need_k, bool need_v, bool need_o) {
+  const int64_t C = (int64_t)t->n_heads * t->head_dim;
+  const int64_t es = t->io_dtype == P2P_DTYPE_F32 ? 4 : 2;
+  const struct { bool need; int64_t ld, bs; int rows; bool out; } ops[4] = {
+      {need_q, t->q_row_stride, t->q_batch_stride, t->n_query, false},
+      {need_k, t->k_row_stride, t->k_batch_stride, t->n_key, false},
+      {need_v, t->v_row_stride, t->v_batch_stride, t->n_key, false},
+      {need_o, t->o_row_stride, t->o_batch_stride, t->n_query, true}};
+  for (const auto& op : ops) {
+    if (!op.need) continue;
+    if (op.ld < C || op.ld > INT32_MAX || op.bs < 0) return P2P_E_ARG;
+    const int64_t span = (int64_t)(op.rows - 1) * op.ld + C;   // (< 2^62: rows and ld are below 2^31)
+    if (span * es > INT32_MAX) return P2P_E_ARG;
+    if (op.out && t->n_batch > 1 && op.bs < span) return P2P_E_ARG;
+  }
+  return 0;
+}
+
 void no_maps(SelfArgs& a) { a.n_maps = 0; }
 void no_maps(CrossArgs&) {}
 
@@ -130,7 +161,7 @@ int fill_self(SelfArgs& a, const p2p_attn_tensors* t, const int32_t* qk_src, flo
     a.store_accumulate = store_accumulate ? 1 : 0;
     a.lse = lse_workspace;
   }
-  return 0;
+  return check_layout(t, true, true, true, true);
 }
 
 // p2p_attn_fwd_lse's arguments, validated, as SelfArgs
@@ -149,7 +180,7 @@ int fill_self_lse(SelfArgs& a, const p2p_attn_tensors* t, float* lse) {
     a.qk_src[n] = n;
     a.store_slot[n] = -1;
   }
-  return 0;
+  return check_layout(t, true, true, true, true);
 }
 
 // p2p_cross_attn_fwd's arguments, validated, as the kernels' CrossArgs
@@ -223,7 +254,7 @@ int fill_cross(CrossArgs& a, const p2p_attn_tensors* t, const p2p_group* groups,
       if (groups[g].flags & P2P_PROGRAM_F_DENSE) a.edit_dense = 1;
       else a.edit_terms = 1;
     }
-  return 0;
+  return check_layout(t, true, true, true, true);
 }
 
 }  // namespace
@@ -285,6 +316,8 @@ int p2p_attn_probs(const p2p_attn_tensors* t, const uint8_t* key_mask, float* pr
   int rc = check_tensors(t, true, true, false, false);
   if (rc) return rc;
   if (!probs) return P2P_E_ARG;
+  rc = check_layout(t, true, true, false, false);
+  if (rc) return rc;
   SelfArgs a;
   fill_common(a, t);
   a.variant = self_variant();
@@ -304,6 +337,8 @@ int p2p_attn_pv(const p2p_attn_tensors* t, const float* probs, p2p_stream_t stre
   int rc = check_tensors(t, false, false, true, true);
   if (rc) return rc;
   if (!probs) return P2P_E_ARG;
+  rc = check_layout(t, false, false, true, true);
+  if (rc) return rc;
   SelfArgs a;
   fill_common(a, t);
   a.variant = 0;
@@ -351,6 +386,10 @@ int p2p_attn_bwd(const p2p_attn_tensors* t, const void* dout, const float* lse, 
   if (need > 0 && !aligned16(workspace)) return P2P_E_ALIGN;
   if (t->compute != P2P_COMPUTE_BF16) return P2P_E_DTYPE;
   if (!aligned16(dout) || !aligned16(dq) || !aligned16(dk) || !aligned16(dv)) return P2P_E_ALIGN;
+  if (!bwd_head_dim_compiled(t->head_dim)) return P2P_E_HEAD_DIM;
+  // dout / dq share o's / q's layout: the contract covers them
+  rc = check_layout(t, true, true, true, true);
+  if (rc) return rc;
   BwdArgs a;
   a.q = t->q; a.k = t->k; a.v = t->v; a.o = t->o; a.dout = dout;
   a.dq = dq; a.dk = dk; a.dv = dv; a.lse = lse; a.delta = delta;
@@ -427,6 +466,8 @@ static int text_attn_fwd(const p2p_attn_tensors* t, bool causal, const int32_t* 
   // (check_tensors has rejected 16-bit tensors with the exact-f32 check mode)
   if (t->io_dtype != P2P_DTYPE_BF16 && t->io_dtype != P2P_DTYPE_F16) return P2P_E_DTYPE;
   if ((uintptr_t)key_counts & 3) return P2P_E_ALIGN;
+  const int rl = check_layout(t, true, true, true, true);
+  if (rl) return rl;
   TextAttnArgs a;
   a.q = t->q; a.k = t->k; a.v = t->v; a.o = t->o;
   a.ldq = t->q_row_stride; a.ldk = t->k_row_stride; a.ldv = t->v_row_stride; a.ldo = t->o_row_stride;

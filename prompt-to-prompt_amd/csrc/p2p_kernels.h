@@ -145,6 +145,17 @@ struct BwdArgs {
   int kv_f32;                  // dk/dv are f32 buffers
   float* ws;                   // [2 (dK, dV)][kv_split][N][K][H*D] f32 partials when kv_split > 1
 };
+// the head dims with compiled backward kernels (dispatch_bwd's cases)
+#define P2P_FOR_EACH_BWD_D(X) X(40) X(64) X(80) X(160)
+inline bool bwd_head_dim_compiled(int d) {
+  switch (d) {
+#define P2P_CASE(DD) case DD:
+    P2P_FOR_EACH_BWD_D(P2P_CASE)
+#undef P2P_CASE
+    return true;
+    default: return false;
+  }
+}
 int run_attn_bwd(const BwdArgs& a, int io_dtype, int d, hipStream_t st);
 int bwd_kv_split(int N, int H, int P, int K, int d);   // launcher's query split (workspace sizing)
 int run_store_scale(const float* src, float* dst, float divisor, int64_t n, hipStream_t st);

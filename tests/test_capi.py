@@ -136,3 +136,100 @@ def test_production_library_ignores_variant_env(monkeypatch):
     import subprocess
     out = subprocess.run(["strings", _hip.library_path()], capture_output=True, text=True).stdout
     assert "P2P_SELF_VARIANT" not in out
+
+
+# ---------------------------------------------------------------------------- operand layout contract
+# include/p2p_hip.h: for every operand a call needs, row stride >= n_heads * head_dim, batch stride
+# >= 0 (0 is a broadcast entry, legal on q / k / v), o's batch entries apart, and the operand's span
+# within a 32-bit byte offset -- else P2P_E_ARG, before anything is launched.
+C, ROWS_Q, ROWS_K = 320, 4096, 77           # _tensors' channels; the rows the calls below see
+G_ALL = (_hip.Group * 1)()
+G_ALL[0].first, G_ALL[0].count = 0, 8
+
+LAYOUT_CALLS = {   # entry point -> (operands it needs, the call with dummy pointers)
+    "p2p_self_attn_fwd": ("qkvo", lambda L, t: L.p2p_self_attn_fwd(ctypes.byref(t), None, None, None, 0, None, None)),
+    "p2p_cross_attn_fwd": ("qkvo", lambda L, t: L.p2p_cross_attn_fwd(ctypes.byref(t), G_ALL, 1, None, None, 0, None)),
+    "p2p_attn_probs": ("qk", lambda L, t: L.p2p_attn_probs(ctypes.byref(t), None, 64, None)),
+    "p2p_attn_pv": ("vo", lambda L, t: L.p2p_attn_pv(ctypes.byref(t), 64, None)),
+    "p2p_attn_fwd_lse": ("qkvo", lambda L, t: L.p2p_attn_fwd_lse(ctypes.byref(t), 64, None)),
+}
+
+
+def _layout_tensors(**kw):
+    """_tensors with n_key = 77 (what the cross call takes) and k / v batch strides to match."""
+    base = dict(n_key=ROWS_K, k_batch_stride=C * ROWS_K, v_batch_stride=C * ROWS_K)
+    base.update(kw)
+    return _tensors(**base)
+
+
+def _layout_violations(op, es=4):
+    rows = ROWS_Q if op in "qo" else ROWS_K
+    wide = 1 << 24                          # 76 rows x 2^24 elements x 2 bytes is already past INT32_MAX
+    bad = {
+        "rows_overlap": {f"{op}_row_stride": C - 8},
+        "negative_row_stride": {f"{op}_row_stride": -C},
+        "negative_batch_stride": {f"{op}_batch_stride": -C * rows},
+        # batch entries apart, so that nothing but the span is wrong
+        "span_past_int32": {f"{op}_row_stride": wide, f"{op}_batch_stride": wide * rows},
+    }
+    if op == "o":
+        bad["batch_entries_overlap"] = {"o_batch_stride": (rows - 1) * C + C - 8}
+        bad["zero_batch_stride_on_o"] = {"o_batch_stride": 0}
+    return bad
+
+
+LAYOUT_REJECTS = [pytest.param(fn, kw, id=f"{fn}-{op}-{rule}") for fn, (needs, _) in LAYOUT_CALLS.items()
+                  for op in needs for rule, kw in _layout_violations(op).items()]
+
+
+@pytest.mark.parametrize("fn,kw", LAYOUT_REJECTS)
+def test_attn_rejects_a_layout_violation(fn, kw):
+    L = _hip.lib()
+    call = LAYOUT_CALLS[fn][1]
+    assert call(L, _layout_tensors(io_dtype=1, **kw)) == -1
+    # the same violation on 4-byte elements (the autograd forward and the check mode take them)
+    assert call(L, _layout_tensors(**kw)) == -1
+
+
+def test_layout_rules_through_the_selection_query():
+    """The queries validate as the forward calls do and launch nothing, so they can also show what the
+    rules ACCEPT: the exact span limit, broadcast q / k / v entries, one batch entry of o."""
+    def accepted(**kw):
+        return _hip.self_attn_kernel(_tensors(**kw)) is not None
+
+    assert accepted()
+    # f32, P = K = 4096, C = 320: (4095 ld + 320) x 4 <= INT32_MAX  <=>  ld <= 131103
+    for op in "qkvo":
+        assert accepted(**{f"{op}_row_stride": 131100, f"{op}_batch_stride": 131100 * 4096})
+        assert not accepted(**{f"{op}_row_stride": 131104, f"{op}_batch_stride": 131104 * 4096})
+    assert accepted(q_batch_stride=0, k_batch_stride=0, v_batch_stride=0)
+    assert not accepted(o_batch_stride=0)
+    assert accepted(o_batch_stride=0, n_batch=1)
+    assert accepted(o_batch_stride=4095 * 320 + 320) and not accepted(o_batch_stride=4095 * 320 + 320 - 4)
+    # padded rows: the bound follows the row stride in use
+    assert accepted(o_row_stride=328, o_batch_stride=4095 * 328 + 320)
+    assert not accepted(o_row_stride=328, o_batch_stride=4095 * 328 + 320 - 8)
+
+
+def test_production_strides_pass_the_layout_rules():
+    """What ptp_utils._project hands the kernels: q, k, v column slices of one [N, P, 3C] projection
+    (self), k, v slices of the cached [N, 77, 2C] one (cross), bf16, and the largest span the product
+    has (P = 4096 rows of 1536 elements, 12 MB)."""
+    P = 4096
+    t = _tensors(io_dtype=1, q_row_stride=3 * C, k_row_stride=3 * C, v_row_stride=3 * C, q_batch_stride=3 * C * P,
+                 k_batch_stride=3 * C * P, v_batch_stride=3 * C * P, q=16, k=16 + 2 * C, v=16 + 4 * C)
+    assert _hip.self_attn_kernel(t) == "self40_kernel<40,8,2,256>"
+    assert _hip.self_attn_kernel(t, keeps_maps=True) == "self_attn_fused_kernel<…,D,64,8,EXACT>"
+    t = _tensors(io_dtype=1, n_key=77, k_row_stride=2 * C, v_row_stride=2 * C, k_batch_stride=2 * C * 77,
+                 v_batch_stride=2 * C * 77, k=16, v=16 + 2 * C)
+    G = (_hip.Group * 2)()
+    G[0].first, G[0].count = 0, 4
+    G[1].first, G[1].count = 4, 4
+    assert _hip.cross_attn_kernel(t, G) == "cross_group_kernel<D,4>"
+    # the uncond prompts as one broadcast entry
+    t.k_batch_stride = t.v_batch_stride = 0
+    assert _hip.cross_attn_kernel(t, G) == "cross_group_kernel<D,4>"
+    t = _tensors(io_dtype=1, n_heads=8, head_dim=64, q_row_stride=1536, k_row_stride=1536, v_row_stride=1536,
+                 o_row_stride=512, q_batch_stride=1536 * P, k_batch_stride=1536 * P, v_batch_stride=1536 * P,
+                 o_batch_stride=512 * P)
+    assert _hip.self_attn_kernel(t) == "self_attn_fused_kernel<…,D,64,4>"

@@ -63,3 +63,31 @@ def test_latent_step_dtype_range():
     assert bad == -3
     a.eps_dtype = 3
     assert L.p2p_latent_step(ctypes.byref(a), None) == bad
+
+
+def test_layout_rules_count_f16_as_two_bytes():
+    """The operand layout contract (include/p2p_hip.h) with float16 tensors: the span limit counts
+    2-byte elements, and production's fused-projection strides pass."""
+    from test_capi import LAYOUT_CALLS, _layout_tensors, _layout_violations
+
+    def accepted(**kw):
+        return _hip.self_attn_kernel(_tensors(io_dtype=2, **kw)) is not None
+
+    # P = K = 4096, C = 320: (4095 ld + 320) x 2 <= INT32_MAX  <=>  ld <= 262207 (twice the f32 limit)
+    for op in "qkvo":
+        assert accepted(**{f"{op}_row_stride": 262200, f"{op}_batch_stride": 262200 * 4096})
+        assert not accepted(**{f"{op}_row_stride": 262208, f"{op}_batch_stride": 262208 * 4096})
+    assert accepted(q_row_stride=960, k_row_stride=960, v_row_stride=960, q_batch_stride=960 * 4096,
+                    k_batch_stride=960 * 4096, v_batch_stride=960 * 4096)
+    assert _hip.self_attn_kernel(_tensors(io_dtype=2, q_row_stride=960, k_row_stride=960, v_row_stride=960,
+                                          q_batch_stride=960 * 4096, k_batch_stride=960 * 4096,
+                                          v_batch_stride=960 * 4096)) == "self40_kernel<40,8,2,256,H16>"
+    # every rule, every operand, through the forward entry points that take float16
+    L = _hip.lib()
+    for fn in ("p2p_self_attn_fwd", "p2p_cross_attn_fwd", "p2p_attn_probs", "p2p_attn_pv"):
+        needs, call = LAYOUT_CALLS[fn]
+        for op in needs:
+            for rule, kw in _layout_violations(op).items():
+                assert call(L, _layout_tensors(io_dtype=2, **kw)) == -1, (fn, op, rule)
+    # the autograd forward still answers the dtype first
+    assert LAYOUT_CALLS["p2p_attn_fwd_lse"][1](L, _layout_tensors(io_dtype=2, q_row_stride=312)) == -3

@@ -34,6 +34,14 @@ def o_tol(v, compute):
     return (2.0 ** -7 if compute == "bf16" else 1e-5) * v.float().abs().max().item()
 
 
+# The other bounds of this file by name, for the tests that import them (test_gpu_layouts.py); the
+# tests below state the same figures where they use them.  Stored probabilities per compute mode (one
+# call; an accumulated store of n calls is held to n times it), and the LocalBlend word sums of
+# test_cross_group_kernel_bf16 (two accumulated calls).
+PROB_TOL = {"bf16": 2e-3, "f32": 1e-5}
+WORD_SUM_TOL = 2e-2
+
+
 def make_qkv(N, P, K, heads, d, dtype, qscale=1.0, seed=0, dev="cuda"):
     g = torch.Generator(device=dev).manual_seed(seed)
     C = heads * d
