@@ -554,6 +554,80 @@ typedef struct {
 
 int p2p_map_panels(const p2p_map_panels_args* a, p2p_stream_t stream);
 
+/* Batched null-text inversion (null_text.py:574-606 for B images in one U-Net call; p2p_amd/
+ * null_text.py NullInversion.invert_batch), additive to ABI 16: new symbols only.  Both entry points
+ * take B images of one size, keep one flag byte per image on the device (active: nonzero = still
+ * optimising) and never involve the host, so they can sit in a captured graph. */
+
+/* The guided DDIM prev_step, the per-image MSE against the inverted trajectory and its gradient
+ * with respect to eps_u, in one launch (null_text.py:588-591 and the backward of those lines).
+ * Per element, in f32 on the widened inputs, with c = coef[0..3] = sqrt(1 - a_t), sqrt(a_t),
+ * sqrt(a_prev), sqrt(1 - a_prev) (DDIMScheduler.prev_coeffs, read from DEVICE memory so that a
+ * graph captured once is refilled per DDIM step):
+ *   eps  = eps_u + guidance * (eps_c - eps_u)
+ *   prev = c2 * ((x - c0 * eps) / c1) + c3 * eps
+ *   r    = prev - target
+ *   loss[b] = mean(r^2) over image b's n elements
+ *   grad_eps_u = (2 / n) * (1 - guidance) * (c3 - c2 * c0 / c1) * r
+ * The scalar in front of r is formed in f64 and rounded to f32; the f32 product is rounded once to
+ * the eps dtype.  The squares are summed in f64 in a fixed order, without atomics: image b's loss
+ * and gradient bits depend on its own data only, not on B nor on its place in the batch, and are
+ * the same from launch to launch.  Where active[b] == 0 the gradient is exact (+0) zeros; the loss
+ * is written all the same.
+ * Rejected before anything is launched: a null pointer, B <= 0 or n <= 0 (P2P_E_ARG); an eps_dtype
+ * other than P2P_DTYPE_F32 / P2P_DTYPE_BF16 (P2P_E_DTYPE: fp16 too, as the attention backward this
+ * gradient feeds refuses it); B > 65535 (P2P_E_BATCH); n % 4 != 0, or eps_u / eps_c / x / target /
+ * coef / grad_eps_u off 16 bytes, or loss off 4 (P2P_E_ALIGN). */
+typedef struct {
+  const void* eps_u;      /* [B, n] in eps_dtype                                        */
+  const void* eps_c;      /* [B, n] in eps_dtype                                        */
+  int32_t eps_dtype;      /* P2P_DTYPE_F32 / P2P_DTYPE_BF16                             */
+  float guidance;
+  const float* x;         /* [B, n] the current latent                                  */
+  const float* target;    /* [B, n] the inverted trajectory's previous latent           */
+  const float* coef;      /* 4 f32, device                                              */
+  const uint8_t* active;  /* [B], device                                                */
+  float* loss;            /* [B] out                                                    */
+  void* grad_eps_u;       /* [B, n] out, in eps_dtype                                   */
+  int32_t B, n;
+} P2PNullLossArgs;
+
+int p2p_null_loss(const P2PNullLossArgs* a, p2p_stream_t stream);
+
+/* One Adam step per image, gated, then the early stop of null_text.py:597.  For every image whose
+ * flag is set AT LAUNCH, torch.optim.Adam's update (t = step[b] + 1):
+ *   m <- beta1 m + (1 - beta1) g,   v <- beta2 v + (1 - beta2) g^2
+ *   p <- p - lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   step[b] += 1,  steps_run[b] += 1
+ * and then active[b] &= !(loss[b] < threshold[b]), a strict < in f32: the update of the step whose
+ * loss met the threshold IS applied (the reference breaks after optimizer.step()).  Nothing of an
+ * image whose flag is clear at launch is written: its param, both moments, step and steps_run keep
+ * their bits.  The bias corrections and 1 - beta are formed in f64, as torch forms them in Python
+ * floats, and then used as f32 scalars; beta1, beta2 and eps are therefore doubles (0.999f is not
+ * 0.999: 1 - beta2^t would be off by 1e-5 of its value).
+ * The flags and step counts are read by every workgroup of the update, so the update does not
+ * write them: the entry point launches a second, one-thread-per-image kernel behind it on the same
+ * stream, which advances the counts and clears the flags (no ping-pong buffers).
+ * Rejected before anything is launched: a null pointer, B <= 0, m <= 0, a beta outside [0, 1) or a
+ * negative eps (P2P_E_ARG); B > 65535 (P2P_E_BATCH); m % 4 != 0, param / grad / exp_avg /
+ * exp_avg_sq off 16 bytes, or lr / step / loss / threshold / steps_run off 4 (P2P_E_ALIGN). */
+typedef struct {
+  float* param;            /* [B, m] in/out                                             */
+  const float* grad;       /* [B, m]                                                    */
+  float* exp_avg;          /* [B, m] in/out                                             */
+  float* exp_avg_sq;       /* [B, m] in/out                                             */
+  const float* lr;         /* device scalar                                             */
+  int32_t* step;           /* [B] in/out: Adam's step count, reset per DDIM step        */
+  uint8_t* active;         /* [B] in/out                                                */
+  const float* loss;       /* [B], as p2p_null_loss wrote it                            */
+  const float* threshold;  /* [B]: early_stop_epsilon_b + i * 2e-5, refilled per step   */
+  int32_t* steps_run;      /* [B] in/out: updates applied since the caller zeroed it    */
+  int32_t B, m;
+  double beta1, beta2, eps; /* torch's defaults: 0.9, 0.999, 1e-8                       */
+} P2PNullAdamArgs;
+
+int p2p_null_adam(const P2PNullAdamArgs* a, p2p_stream_t stream);
+
 /* Measurement only (ABI 15; bench.py's roofline clock, not part of the reference's interface):
  * n_workgroups one-wave workgroups each read the shader-cycle counter and the constant 100 MHz
  * counter, spin until `ticks` (1..1e6) of the 100 MHz counter have passed, and read both again:

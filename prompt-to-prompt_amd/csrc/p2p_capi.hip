@@ -511,6 +511,16 @@ int p2p_map_panels(const p2p_map_panels_args* a, p2p_stream_t stream) {
   return run_map_panels(*a, (hipStream_t)stream);
 }
 
+int p2p_null_loss(const P2PNullLossArgs* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_null_loss(*a, (hipStream_t)stream);
+}
+
+int p2p_null_adam(const P2PNullAdamArgs* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_null_adam(*a, (hipStream_t)stream);
+}
+
 int p2p_clock_probe(uint64_t* out, int32_t n_workgroups, int32_t ticks, p2p_stream_t stream) {
   if (!out || n_workgroups < 1 || n_workgroups > 1024 || ticks < 1 || ticks > 1000000) return P2P_E_ARG;
   return run_clock_probe(reinterpret_cast<unsigned long long*>(out), n_workgroups, ticks, (hipStream_t)stream);

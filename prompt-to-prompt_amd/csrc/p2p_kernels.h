@@ -209,6 +209,9 @@ int run_bias_act(const p2p_bias_act_args& a, bool erf, hipStream_t st);   // qui
 // the attention-map figures (p2p_viz.hip): every argument check happens in these, before the launch
 int run_maps_aggregate(const p2p_maps_aggregate_args& a, hipStream_t st);
 int run_map_panels(const p2p_map_panels_args& a, hipStream_t st);
+// batched null-text inversion (p2p_null.hip): every argument check happens in these, before the launch
+int run_null_loss(const P2PNullLossArgs& a, hipStream_t st);
+int run_null_adam(const P2PNullAdamArgs& a, hipStream_t st);
 int run_clock_probe(unsigned long long* out, int n_wg, int ticks, hipStream_t st);
 
 }  // namespace p2p

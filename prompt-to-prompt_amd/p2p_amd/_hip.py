@@ -188,6 +188,25 @@ class MapPanelsArgs(ctypes.Structure):
     ]
 
 
+class NullLossArgs(ctypes.Structure):
+    _fields_ = [
+        ("eps_u", ctypes.c_void_p), ("eps_c", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32),
+        ("guidance", ctypes.c_float), ("x", ctypes.c_void_p), ("target", ctypes.c_void_p), ("coef", ctypes.c_void_p),
+        ("active", ctypes.c_void_p), ("loss", ctypes.c_void_p), ("grad_eps_u", ctypes.c_void_p),
+        ("B", ctypes.c_int32), ("n", ctypes.c_int32),
+    ]
+
+
+class NullAdamArgs(ctypes.Structure):
+    _fields_ = [
+        ("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+        ("exp_avg_sq", ctypes.c_void_p), ("lr", ctypes.c_void_p), ("step", ctypes.c_void_p),
+        ("active", ctypes.c_void_p), ("loss", ctypes.c_void_p), ("threshold", ctypes.c_void_p),
+        ("steps_run", ctypes.c_void_p), ("B", ctypes.c_int32), ("m", ctypes.c_int32),
+        ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+    ]
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -233,6 +252,8 @@ def lib():
         L.p2p_image_to_model.argtypes = [ctypes.POINTER(ImageToModelArgs), vp]
         L.p2p_maps_aggregate.argtypes = [ctypes.POINTER(MapsAggregateArgs), vp]
         L.p2p_map_panels.argtypes = [ctypes.POINTER(MapPanelsArgs), vp]
+        L.p2p_null_loss.argtypes = [ctypes.POINTER(NullLossArgs), vp]
+        L.p2p_null_adam.argtypes = [ctypes.POINTER(NullAdamArgs), vp]
         L.p2p_clock_probe.argtypes = [vp, i32, i32, vp]
         L.p2p_set_launch_events.argtypes = [vp, vp]
         if L.p2p_abi_version() != ABI_VERSION:
@@ -263,7 +284,7 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_self_attn_kernel", "p2p_cross_attn_kernel", "p2p_plms_step", "p2p_image_u8",
                     "p2p_image_to_model", "p2p_group_norm_stats_floats", "p2p_causal_attn_fwd", "p2p_layer_norm",
                     "p2p_bias_quick_gelu", "p2p_text_attn_fwd", "p2p_bias_gelu", "p2p_maps_aggregate",
-                    "p2p_map_panels")
+                    "p2p_map_panels", "p2p_null_loss", "p2p_null_adam")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -662,6 +683,56 @@ def attn_bwd(q, k, v, o, dout, lse, heads, scale, dq, dk, dv, delta, workspace=N
     rc = lib().p2p_attn_bwd(ctypes.byref(t), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(),
                             dk.data_ptr(), dv.data_ptr(), kv_f32, ws_ptr, need, _stream(q.device))
     _check(rc, "p2p_attn_bwd")
+
+
+def _dense(what: str, t: torch.Tensor, dtype, numel: int):
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
+        raise HipError(f"{what}: needs a contiguous {dtype} tensor of {numel} elements, "
+                       f"got {t.dtype} {tuple(t.shape)}")
+
+
+def null_loss(eps_u, eps_c, x, target, coef, guidance: float, active, loss, grad_eps_u):
+    """p2p_null_loss for B images: eps_u / eps_c / grad_eps_u [B, ...] in one dtype (f32 or bf16),
+    x / target f32 of the same shape, coef f32 [4] on the device, active uint8 [B]; writes loss
+    f32 [B] and grad_eps_u.  Launches on the current stream, nothing is read back."""
+    _require_cuda(eps_u, eps_c, x, target, coef, active, loss, grad_eps_u)
+    B = eps_u.shape[0]
+    n = eps_u.numel() // max(B, 1)
+    for name, t, dt in (("eps_u", eps_u, eps_u.dtype), ("eps_c", eps_c, eps_u.dtype), ("x", x, torch.float32),
+                        ("target", target, torch.float32), ("grad_eps_u", grad_eps_u, eps_u.dtype)):
+        _dense(f"null_loss {name}", t, dt, B * n)
+    _dense("null_loss coef", coef, torch.float32, 4)
+    _dense("null_loss active", active, torch.uint8, B)
+    _dense("null_loss loss", loss, torch.float32, B)
+    a = NullLossArgs()
+    a.eps_u, a.eps_c, a.eps_dtype, a.guidance = eps_u.data_ptr(), eps_c.data_ptr(), _dtype_code(eps_u), float(guidance)
+    a.x, a.target, a.coef, a.active = x.data_ptr(), target.data_ptr(), coef.data_ptr(), active.data_ptr()
+    a.loss, a.grad_eps_u, a.B, a.n = loss.data_ptr(), grad_eps_u.data_ptr(), B, n
+    _check(lib().p2p_null_loss(ctypes.byref(a), _stream(x.device)), "p2p_null_loss")
+    return loss, grad_eps_u
+
+
+def null_adam(param, grad, exp_avg, exp_avg_sq, lr, step, active, loss, threshold, steps_run,
+              beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+    """p2p_null_adam: torch.optim.Adam's step on param [B, ...] f32 for every image whose active
+    byte is set, then the early stop (active[b] &= !(loss[b] < threshold[b])); lr is an f32 device
+    scalar, step / steps_run int32 [B], active uint8 [B], loss / threshold f32 [B].  All in place."""
+    _require_cuda(param, grad, exp_avg, exp_avg_sq, lr, step, active, loss, threshold, steps_run)
+    B = param.shape[0]
+    m = param.numel() // max(B, 1)
+    for name, t in (("param", param), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        _dense(f"null_adam {name}", t, torch.float32, B * m)
+    _dense("null_adam lr", lr, torch.float32, 1)
+    for name, t, dt in (("step", step, torch.int32), ("steps_run", steps_run, torch.int32),
+                        ("active", active, torch.uint8), ("loss", loss, torch.float32),
+                        ("threshold", threshold, torch.float32)):
+        _dense(f"null_adam {name}", t, dt, B)
+    a = NullAdamArgs()
+    a.param, a.grad, a.exp_avg, a.exp_avg_sq = param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    a.lr, a.step, a.active, a.loss = lr.data_ptr(), step.data_ptr(), active.data_ptr(), loss.data_ptr()
+    a.threshold, a.steps_run, a.B, a.m = threshold.data_ptr(), steps_run.data_ptr(), B, m
+    a.beta1, a.beta2, a.eps = float(beta1), float(beta2), float(eps)
+    _check(lib().p2p_null_adam(ctypes.byref(a), _stream(param.device)), "p2p_null_adam")
 
 
 # -- U-Net glue (p2p_unet.hip).  Each returns its output, or None when the library reports the

@@ -381,6 +381,188 @@ class NullInversion:
         uncond_embeddings = self.null_optimization(ddim_latents, num_inner_steps, early_stop_epsilon)
         return (image_gt, image_rec), ddim_latents[-1], uncond_embeddings
 
+    def invert_batch(self, images, prompts, offsets=(0, 0, 0, 0), num_inner_steps=10, early_stop_epsilon=1e-5,
+                     verbose=False):
+        """``invert`` for B images in one U-Net batch.  ``images``: B file paths, uint8 arrays or
+        [1, 4, h, w] latents, or one [B, 4, h, w] latent tensor; ``prompts``: B strings;
+        ``early_stop_epsilon``: one float or B of them.  Returns B tuples, each what ``invert``
+        returns for that image: ((image_gt, image_rec), x_T [1, 4, h, w], num_ddim_steps x [1, 77, C]).
+
+        Every image has its own loss, Adam state and early stop (null_text.py:591-598 per image):
+        the stop flags live on the device, p2p_null_loss / p2p_null_adam freeze an image that
+        stopped while the others go on, and the host reads the B flag bytes once per inner step
+        (where ``invert`` reads the loss).  A batch runs until its last image stops.
+        ``inner_steps_run_per_image`` holds the Adam updates each image took."""
+        if torch.is_tensor(images) and images.dim() == 4:
+            images = [images[b:b + 1] for b in range(images.shape[0])]
+        images, prompts = list(images), list(prompts)
+        B = len(images)
+        if B == 0 or len(prompts) != B:
+            raise ValueError(f"invert_batch: {B} images for {len(prompts)} prompts")
+        try:
+            epsilons = [float(e) for e in early_stop_epsilon]
+        except TypeError:
+            epsilons = [float(early_stop_epsilon)] * B
+        if len(epsilons) != B:
+            raise ValueError(f"invert_batch: {len(epsilons)} early_stop_epsilon values for {B} images")
+        if getattr(self.model.unet, "dtype", None) == torch.float16:
+            raise NotImplementedError("the attention backward takes float32 or bfloat16 tensors, not float16 "
+                                      "(run the differentiated U-Net in bfloat16 or float32)")
+        images_gt = [load_512(im, *offsets) if isinstance(im, str) else im for im in images]
+        latents = [self.image2latent(im) for im in images_gt]
+        if any(x.shape != latents[0].shape or x.shape[0] != 1 for x in latents):
+            raise ValueError(f"invert_batch: the latents must share one size, got {[tuple(x.shape) for x in latents]}")
+        from . import ptp_utils
+        self._init_prompts(prompts)
+        ptp_utils.register_attention_control(self.model, None)
+        if verbose:
+            print("DDIM inversion...")
+        images_rec = [self.latent2image(x) for x in latents]
+        ddim_latents = self.ddim_loop(torch.cat(latents))
+        if verbose:
+            print("Null-text optimization...")
+        embs = self._null_optimization_batch(ddim_latents, num_inner_steps, epsilons)
+        return [((images_gt[b], images_rec[b]), ddim_latents[-1][b:b + 1], [e[b:b + 1] for e in embs])
+                for b in range(B)]
+
+    @torch.no_grad()
+    def _init_prompts(self, prompts):
+        """init_prompt for a batch: context = [B null rows (the embedding of ""), B conditional rows]."""
+        def encode(texts):
+            ids = self.tokenizer(texts, padding="max_length", max_length=self.tokenizer.model_max_length,
+                                 truncation=True, return_tensors="pt").input_ids
+            return self.model.text_encoder(ids.to(self.model.device))[0]
+        null = encode([""]).expand(len(prompts), -1, -1)
+        self.context = torch.cat([null, encode(list(prompts))])
+        self.prompt = list(prompts)
+
+    def _null_optimization_batch(self, latents, num_inner_steps, epsilons):
+        """null_optimization for latents [B, 4, h, w]: per DDIM step one batch-B eps_c, up to
+        num_inner_steps runs of _BatchedNullStep (one graph replay each with use_graphs), then the
+        guided prev_step of the batch with the optimised embeddings (a U-Net call of batch 2B)."""
+        uncond, cond = self.context.chunk(2)
+        unet = self.model.unet
+        latent_cur = latents[-1]
+        dev = latent_cur.device
+        graphed = self.use_graphs and latent_cur.is_cuda
+        t0 = self.scheduler.timesteps[0]
+        step = _BatchedNullStep(self, latent_cur, uncond, graphed)
+        if graphed:
+            fwd_c = _GraphedForward(unet, latent_cur, cond, t0)
+            fwd_cfg = _GraphedForward(unet, torch.cat([latent_cur] * 2), torch.cat([uncond, cond]), t0)
+        else:
+            def fwd_c(x, t, ctx):
+                with torch.no_grad():
+                    return unet(x, t, encoder_hidden_states=ctx)["sample"]
+            fwd_cfg = fwd_c
+        eps64 = torch.tensor(epsilons, dtype=torch.float64)
+        per_step = []
+        for i in range(self.num_ddim_steps):
+            latent_prev = latents[len(latents) - i - 2]
+            t = self.scheduler.timesteps[i]
+            eps_c = fwd_c(latent_cur, t, cond)
+            # the reference's Python-float threshold epsilon + i * 2e-5, rounded once to the f32 the
+            # device compares the f32 loss with
+            threshold = (eps64 + i * 2e-5).to(torch.float32).to(dev)
+            step.reset(uncond, 1e-2 * (1.0 - i / 100.0), latent_cur, eps_c, latent_prev, t, threshold)
+            for _ in range(num_inner_steps):
+                step.run()
+                if not step.active.cpu().any():      # the one read-back per inner step
+                    break
+            uncond = step.param.detach().clone()
+            per_step.append(uncond)
+            with torch.no_grad():
+                eps = fwd_cfg(torch.cat([latent_cur] * 2), t, torch.cat([uncond, cond]))
+                eps_u, eps_cc = eps.chunk(2)
+                latent_cur = self.prev_step(eps_u + self.guidance_scale * (eps_cc - eps_u), t, latent_cur)
+        self.inner_steps_run_per_image = step.steps_run.tolist()
+        return per_step
+
+
+class _BatchedNullStep:
+    """One null-text Adam step for B images (NullInversion._null_optimization_batch): the U-Net
+    forward on the [B, 77, C] null embeddings as the only leaf, p2p_null_loss (guided prev_step,
+    per-image MSE and its gradient with respect to eps_u), the backward from that gradient, and
+    p2p_null_adam (per-image gated Adam, then the early stop) -- captured as one HIP graph, or run
+    eagerly.  Static inputs as _GraphedNullStep's, plus per image the threshold, the active flag, the
+    loss, Adam's step count and the count of updates taken; the flags never leave the device
+    inside a step, so an image that stopped is frozen (embedding and Adam state bit-identical) by
+    the kernels while the same graph goes on replaying for the others."""
+
+    def __init__(self, inv, latent, uncond, graphed):
+        from . import _hip
+        dev = latent.device
+        B = latent.shape[0]
+        unet = inv.model.unet
+        udtype = next(unet.parameters()).dtype
+        self.inv = inv
+        self.x = latent.detach().clone()
+        self.eps_c = torch.zeros_like(self.x, dtype=udtype)
+        self.grad_eps = torch.zeros_like(self.eps_c)
+        self.target = torch.zeros_like(self.x)
+        self.t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.coef = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.param = uncond.detach().clone().float().contiguous().requires_grad_(True)
+        self.param.grad = torch.zeros_like(self.param)
+        self.exp_avg = torch.zeros_like(self.param)
+        self.exp_avg_sq = torch.zeros_like(self.param)
+        self.lr = torch.tensor(1e-2, dtype=torch.float32, device=dev)
+        self.step = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.steps_run = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.active = torch.ones(B, dtype=torch.uint8, device=dev)
+        self.loss = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.threshold = torch.full((B,), -1.0, dtype=torch.float32, device=dev)
+        g = inv.guidance_scale
+
+        def body():
+            self.param.grad.zero_()
+            eps_u = unet(self.x, self.t, encoder_hidden_states=self.param)["sample"].contiguous()
+            _hip.null_loss(eps_u.detach(), self.eps_c, self.x, self.target, self.coef, g, self.active, self.loss,
+                           self.grad_eps)
+            eps_u.backward(self.grad_eps)
+            _hip.null_adam(self.param.detach(), self.param.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.step,
+                           self.active, self.loss, self.threshold, self.steps_run)
+
+        self.run = body
+        if not graphed:
+            return
+        # warm-up on a side stream (autograd buffers, allocator), then capture; reset() refills
+        # everything the warm-up moved but the update counts
+        self.t.fill_(int(inv.scheduler.timesteps[0]))
+        self.coef.copy_(self._coeffs(inv.scheduler.timesteps[0]))
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                body()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            body()
+        self.steps_run.zero_()
+        self.run = self.graph.replay
+
+    def _coeffs(self, t):
+        c = self.inv.scheduler.prev_coeffs(t)        # (sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev)
+        return torch.tensor([float(x) for x in c], dtype=torch.float32)
+
+    @torch.no_grad()
+    def reset(self, uncond, lr, latent, eps_c, target, t, threshold):
+        """A fresh Adam on a fresh copy of the null embeddings (null_text.py:582-584), every image
+        active again."""
+        self.param.copy_(uncond)
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        self.step.zero_()
+        self.active.fill_(1)
+        self.threshold.copy_(threshold)
+        self.lr.fill_(lr)
+        self.x.copy_(latent)
+        self.eps_c.copy_(eps_c)
+        self.target.copy_(target)
+        self.t.fill_(int(t))
+        self.coef.copy_(self._coeffs(t))
+
 
 class _GraphedForward:
     """A no-grad U-Net call on fixed shapes captured as a HIP graph; __call__ refills the static

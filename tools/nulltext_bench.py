@@ -2,7 +2,9 @@
 conditional U-Net, then per DDIM step up to 10 Adam steps on the null embedding with gradients through
 every patched attention -- p2p_attn_fwd_lse / p2p_attn_bwd) followed by the P2P AttentionReplace edit
 with the per-step null embeddings, 512x512 (64x64 latent), synthetic bf16 SD-v1.4-shaped U-Net.
-Prints one JSON line per phase.  Usage: python tools/nulltext_bench.py [ddim_steps] [inner_steps] [conv 0 = MIOpen immediate | 1 = MIOpen find | 2 = no MIOpen]"""
+Prints one JSON line per phase.  Usage: python tools/nulltext_bench.py [ddim_steps] [inner_steps] [conv 0 = MIOpen immediate | 1 = MIOpen find | 2 = no MIOpen] [batch]
+With batch > 1 it times NullInversion.invert_batch on that many different seeds instead (inversion only)
+and prints inversions_per_s."""
 import json
 import os
 import sys
@@ -33,7 +35,33 @@ class CountingUNet(torch.nn.Module):
             return getattr(self.inner, name)
 
 
-def main(steps=50, inner=10, find=0):
+def batch_main(steps, inner, batch):
+    """B different seeds through NullInversion.invert_batch: one JSON line with inversions_per_s and
+    the Adam updates each image took (a batch runs until its last image stops)."""
+    dev = torch.device("cuda")
+    model = pl.SyntheticStableDiffusion(device=dev, dtype=torch.bfloat16)
+    x0 = torch.cat([torch.randn(1, 4, 64, 64, generator=torch.Generator().manual_seed(7 + b)) for b in range(batch)])
+    x0 = x0.to(dev)
+    prompts = ([pl.SOURCE] + list(pl.EDITS) * batch)[:batch]
+    null_text.NullInversion(model, num_ddim_steps=2).invert_batch(x0, prompts, num_inner_steps=1)
+    torch.cuda.synchronize()
+    inv = null_text.NullInversion(model, num_ddim_steps=steps)
+    t0 = time.perf_counter()
+    out = inv.invert_batch(x0, prompts, num_inner_steps=inner, early_stop_epsilon=1e-5)
+    torch.cuda.synchronize()
+    t_inv = time.perf_counter() - t0
+    assert len(out) == batch and all(torch.isfinite(o[1]).all() for o in out)
+    print(json.dumps({"config": "configs[4] null-text inversion, batched", "batch": batch, "ddim_steps": steps,
+                      "max_inner_steps": inner, "graphs": inv.use_graphs, "seconds": round(t_inv, 3),
+                      "adam_steps_per_image": inv.inner_steps_run_per_image, "unet_dtype": "bf16", "latent": "64x64",
+                      "inversions_per_s": round(batch / t_inv, 4)}), flush=True)
+
+
+def main(steps=50, inner=10, find=0, batch=1):
+    if batch > 1:
+        torch.backends.cudnn.benchmark = find == 1
+        torch.backends.cudnn.enabled = find != 2
+        return batch_main(steps, inner, batch)
     # MIOpen immediate mode picks its naive convolution fallback for several batch-1/2 bf16 U-Net
     # shapes (43-63 ms per call, rocprof); find mode (cudnn.benchmark) searches real kernels once
     # (find = 2: bypass MIOpen -- PyTorch's own im2col + GEMM convolutions)
@@ -81,4 +109,4 @@ def main(steps=50, inner=10, find=0):
 
 
 if __name__ == "__main__":
-    main(*(int(x) for x in sys.argv[1:4]))
+    main(*(int(x) for x in sys.argv[1:5]))
