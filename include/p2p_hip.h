@@ -397,6 +397,65 @@ typedef struct {
 
 int p2p_geglu(const p2p_geglu_args* a, p2p_stream_t stream);
 
+/* The glue's backward with respect to its tensors (p2p_amd/unet_grad.py; additive to ABI 16), under
+ * the contract above.  New here: every reduction is taken inside one sample, in an order that
+ * (channels, hw, groups) fix, so a sample's result bits depend neither on n nor on the other
+ * samples (an all-zero dy of one sample gives that sample an exactly zero dx).
+ *
+ * p2p_group_norm_bwd: dx of p2p_group_norm -- not the gradients of gamma, beta or the per-channel
+ * adds.  With xh = ((x + chan_add + chan_bias) - mean) * rstd and z = xh * gamma + beta:
+ *   g = dy * act'(z) (SiLU'(z) = s (1 + z (1 - s)), s = sigmoid(z)),  gh = g * gamma,
+ *   m1 = mean of gh, m2 = mean of gh * xh over the (n, group) slab,  dx = rstd * (gh - m1 - xh * m2).
+ * z and g are recomputed from x and dy; {mean, rstd} are read from `stats`, the head of the
+ * forward's workspace.  Slabs of 262,144 elements or more (the forward's split statistics) are
+ * P2P_E_ARG. */
+typedef struct {
+  const void* x;            /* the forward's x, chan_add, chan_add_stride, chan_bias, gamma, beta */
+  const void* chan_add;
+  int64_t chan_add_stride;
+  const void* chan_bias;
+  const void* gamma;
+  const void* beta;
+  const void* dy;           /* [n, channels, hw], or [n, hw, channels] where the forward stored tokens */
+  const float* stats;       /* {mean, rstd} per (n, group), as the forward left them: n * groups * 2 f32 */
+  void* dx;                 /* [n, channels, hw]                                            */
+  float* workspace;         /* p2p_group_norm_bwd_workspace_floats() f32                    */
+  int32_t n, channels, hw, groups;
+  int32_t act;              /* P2P_ACT_*, the forward's                                     */
+  int32_t dy_layout;        /* P2P_LAYOUT_*, the forward's y_layout                         */
+  int32_t dtype;            /* P2P_DTYPE_BF16 / P2P_DTYPE_F16: every tensor but stats and workspace */
+} p2p_group_norm_bwd_args;
+
+int p2p_group_norm_bwd(const p2p_group_norm_bwd_args* a, p2p_stream_t stream);
+/* f32 elements p2p_group_norm_bwd needs behind `workspace` (a function of the sizes only, the same
+ * for both layouts of dy), or P2P_E_ARG. */
+int64_t p2p_group_norm_bwd_workspace_floats(int32_t n, int32_t channels, int32_t hw, int32_t groups);
+
+/* GEGLU backward: din[m, j] = dout[m, j] * gelu(gate), din[m, d + j] = dout[m, j] * in[m, j] *
+ * (Phi(gate) + gate * phi(gate)), gate = in[m, d + j], the exact erf form.  `in` as the forward's
+ * (row stride a multiple of 8, >= 2 d); dout [rows, d] and din [rows, 2 d] are dense. */
+typedef struct {
+  const void* in;
+  const void* dout;
+  void* din;
+  int64_t in_row_stride;
+  int32_t rows, d;
+  int32_t dtype;
+} p2p_geglu_bwd_args;
+
+int p2p_geglu_bwd(const p2p_geglu_bwd_args* a, p2p_stream_t stream);
+
+/* dst[n, hw, channels] = src[n, channels, hw]: the gradient of p2p_bias_residual's token-major b
+ * (that of a, and both of the NCHW form, are dout itself).  hw % 8 == 0 and channels % 8 == 0. */
+typedef struct {
+  const void* src;
+  void* dst;
+  int32_t n, channels, hw;
+  int32_t dtype;
+} p2p_nchw_to_tokens_args;
+
+int p2p_nchw_to_tokens(const p2p_nchw_to_tokens_args* a, p2p_stream_t stream);
+
 /* The image ends of the pipeline (additive to ABI 16; p2p_amd/ptp_utils.py latent2image /
  * image2latent).  Three channels.  dtype: P2P_DTYPE_F32 / BF16 / F16, anything else is
  * P2P_E_DTYPE.  Both take height * width % 4 == 0 only (four pixels per thread, no scalar tail)

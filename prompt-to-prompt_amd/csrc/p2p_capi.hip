@@ -446,6 +446,26 @@ int p2p_geglu(const p2p_geglu_args* a, p2p_stream_t stream) {
   return run_geglu(*a, (hipStream_t)stream);
 }
 
+int p2p_group_norm_bwd(const p2p_group_norm_bwd_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_group_norm_bwd(*a, (hipStream_t)stream);
+}
+
+int64_t p2p_group_norm_bwd_workspace_floats(int32_t n, int32_t channels, int32_t hw, int32_t groups) {
+  if (n < 1 || channels < 1 || hw < 1 || groups < 1 || channels % groups) return P2P_E_ARG;
+  return gn_bwd_workspace_floats(n, channels, hw, groups);
+}
+
+int p2p_geglu_bwd(const p2p_geglu_bwd_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_geglu_bwd(*a, (hipStream_t)stream);
+}
+
+int p2p_nchw_to_tokens(const p2p_nchw_to_tokens_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_nchw_to_tokens(*a, (hipStream_t)stream);
+}
+
 int p2p_image_u8(const p2p_image_u8_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
   return run_image_u8(*a, (hipStream_t)stream);

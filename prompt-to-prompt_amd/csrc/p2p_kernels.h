@@ -185,6 +185,18 @@ constexpr int64_t gn_stats_floats(int64_t slabs, int64_t slab) {
 int run_group_norm(const p2p_group_norm_args& a, hipStream_t st);
 int run_bias_residual(const p2p_bias_residual_args& a, hipStream_t st);
 int run_geglu(const p2p_geglu_args& a, hipStream_t st);
+// the glue's backward.  From kGnBwdWideRow pixels a channel's row of the NCHW reduce takes a whole
+// workgroup (four waves), below it one wave; token-major dy leaves one partial per 64-pixel tile.
+constexpr int kGnBwdWideRow = 2048;
+constexpr int kGnBwdTile = 64;   // the transpose tile's pixels (kTile of p2p_unet.hip)
+// f32 elements of p2p_group_norm_bwd_args.workspace: {sum g, sum g xh} per (n, channel, part) for
+// the layout with the most parts, then {m1, m2} per slab
+constexpr int64_t gn_bwd_workspace_floats(int64_t n, int64_t channels, int64_t hw, int64_t groups) {
+  return 2 * n * channels * ((hw + kGnBwdTile - 1) / kGnBwdTile) + 2 * n * groups;
+}
+int run_group_norm_bwd(const p2p_group_norm_bwd_args& a, hipStream_t st);
+int run_geglu_bwd(const p2p_geglu_bwd_args& a, hipStream_t st);
+int run_nchw_to_tokens(const p2p_nchw_to_tokens_args& a, hipStream_t st);
 // the image ends (p2p_image.hip): every argument check happens in these, before the launch
 int run_image_u8(const p2p_image_u8_args& a, hipStream_t st);
 int run_image_to_model(const p2p_image_to_model_args& a, hipStream_t st);

@@ -172,8 +172,8 @@ struct ChanCoef {
   float shift, mean, rstd, gamma, beta;
 };
 
-template <bool F16>
-__device__ __forceinline__ ChanCoef chan_coef(const p2p_group_norm_args& a, int n, int c) {
+template <bool F16, typename Args>
+__device__ __forceinline__ ChanCoef chan_coef(const Args& a, int n, int c) {
   const uint16_t* add = static_cast<const uint16_t*>(a.chan_add);
   const uint16_t* bias = static_cast<const uint16_t*>(a.chan_bias);
   const int g = c / (a.channels / a.groups);
@@ -326,6 +326,268 @@ __global__ __launch_bounds__(256) void geglu_kernel(p2p_geglu_args a, int64_t n_
   *reinterpret_cast<u16x8_t*>(static_cast<uint16_t*>(a.out) + m * a.out_row_stride + j) = o;
 }
 
+// ---- backward (with respect to the tensors only: x of GroupNorm, the input of GEGLU, the tokens
+// of the residual).  GroupNorm, for y = act(xh * gamma + beta), xh = ((x + shift) - mean) * rstd:
+//   g = dy * act'(z), gh = g * gamma, m1 = mean_slab(gh), m2 = mean_slab(gh * xh),
+//   dx = rstd * (gh - m1 - xh * m2)
+// in three launches.  The reduce kernels leave {sum g, sum g * xh} per (n, channel, part) -- one
+// part per channel from NCHW dy, one per 64-pixel tile from token-major dy; the fold kernel (one
+// wave per slab) weights them with gamma and leaves {m1, m2} behind the partials; the apply
+// kernels recompute z and g from x and dy.  Every sum is taken inside one sample, in an order
+// that (channels, hw, groups) fix: a sample's bits do not depend on n or on the other samples.
+
+__device__ __forceinline__ float silu_grad(float z) {
+  const float s = 1.f / (1.f + __expf(-z));
+  return s * (1.f + z * (1.f - s));
+}
+
+// xh and g of eight elements of one channel
+template <bool F16, bool SILU>
+__device__ __forceinline__ void gn_bwd_g8(u16x8_t vx, u16x8_t vdy, const ChanCoef& k, float* xh, float* g) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    xh[j] = ((ld16<F16>(vx[j]) + k.shift) - k.mean) * k.rstd;
+    float gj = ld16<F16>(vdy[j]);
+    if (SILU) gj *= silu_grad(xh[j] * k.gamma + k.beta);
+    g[j] = gj;
+  }
+}
+
+template <bool F16, bool SILU>
+__device__ __forceinline__ u16x8_t gn_bwd_dx8(u16x8_t vx, u16x8_t vdy, const ChanCoef& k, float m1, float m2) {
+  float xh[8], g[8];
+  gn_bwd_g8<F16, SILU>(vx, vdy, k, xh, g);
+  u16x8_t o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = st16<F16>(k.rstd * ((g[j] * k.gamma - m1) - xh[j] * m2));
+  return o;
+}
+
+// NCHW dy: T threads (one wave, or the four of a workgroup) per (n, channel) row of hw elements
+template <bool F16, bool SILU, int T>
+__global__ __launch_bounds__(256) void gn_bwd_reduce_nchw_kernel(p2p_group_norm_bwd_args a) {
+  __shared__ float red[8];
+  const int64_t rows = (int64_t)a.n * a.channels;
+  const int64_t row = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T;
+  const int lane = threadIdx.x % T;
+  const int hwv = a.hw >> 3;
+  float s1 = 0.f, s2 = 0.f;
+  if (row < rows) {
+    const int n = (int)(row / a.channels), c = (int)(row - (int64_t)n * a.channels);
+    const ChanCoef k = chan_coef<F16>(a, n, c);
+    const u16x8_t* x = reinterpret_cast<const u16x8_t*>(static_cast<const uint16_t*>(a.x) + row * a.hw);
+    const u16x8_t* dy = reinterpret_cast<const u16x8_t*>(static_cast<const uint16_t*>(a.dy) + row * a.hw);
+    for (int iv = lane; iv < hwv; iv += T) {
+      float xh[8], g[8];
+      gn_bwd_g8<F16, SILU>(x[iv], dy[iv], k, xh, g);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        s1 += g[j];
+        s2 += g[j] * xh[j];
+      }
+    }
+  }
+  for (int o = 32; o; o >>= 1) {
+    s1 += __shfl_xor(s1, o);
+    s2 += __shfl_xor(s2, o);
+  }
+  if (T == 64) {
+    if (lane == 0 && row < rows) {
+      a.workspace[2 * row] = s1;
+      a.workspace[2 * row + 1] = s2;
+    }
+  } else {   // one row per workgroup: the four waves' sums in wave order
+    if ((threadIdx.x & 63) == 0) {
+      red[2 * (threadIdx.x >> 6)] = s1;
+      red[2 * (threadIdx.x >> 6) + 1] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && row < rows) {
+      a.workspace[2 * row] = ((red[0] + red[2]) + red[4]) + red[6];
+      a.workspace[2 * row + 1] = ((red[1] + red[3]) + red[5]) + red[7];
+    }
+  }
+}
+
+// token-major dy [n, hw, C]: the tile is loaded along the channels of a pixel and read back along
+// the pixels of a channel, beside x; eight neighbouring lanes hold a channel's 64 pixels.
+// grid (hw tiles, C tiles, n); partials [n, C, hw tiles, 2]
+template <bool F16, bool SILU>
+__global__ __launch_bounds__(256) void gn_bwd_reduce_tok_kernel(p2p_group_norm_bwd_args a) {
+  __shared__ __attribute__((aligned(16))) uint16_t tile[kTile * kTileLd];   // [pixel][channel]
+  const int p0 = blockIdx.x * kTile, c0 = blockIdx.y * kTile, n = blockIdx.z;
+  const int C = a.channels, hw = a.hw;
+  const uint16_t* dy = static_cast<const uint16_t*>(a.dy) + (int64_t)n * hw * C;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = threadIdx.x + k * 256;
+    const int p = v >> 3, ch = (v & 7) * 8;
+    if (c0 + ch < C && p0 + p < hw)
+      *reinterpret_cast<u16x8_t*>(&tile[p * kTileLd + ch]) =
+          *reinterpret_cast<const u16x8_t*>(dy + (int64_t)(p0 + p) * C + c0 + ch);
+  }
+  __syncthreads();
+  const uint16_t* x = static_cast<const uint16_t*>(a.x) + (int64_t)n * C * hw;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = threadIdx.x + k * 256;
+    const int ch = v >> 3, p = (v & 7) * 8;
+    float s1 = 0.f, s2 = 0.f;
+    if (c0 + ch < C && p0 + p < hw) {
+      const ChanCoef kc = chan_coef<F16>(a, n, c0 + ch);
+      const u16x8_t vx = *reinterpret_cast<const u16x8_t*>(x + (int64_t)(c0 + ch) * hw + p0 + p);
+      u16x8_t vdy;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vdy[j] = tile[(p + j) * kTileLd + ch];
+      float xh[8], g[8];
+      gn_bwd_g8<F16, SILU>(vx, vdy, kc, xh, g);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        s1 += g[j];
+        s2 += g[j] * xh[j];
+      }
+    }
+    for (int o = 4; o; o >>= 1) {
+      s1 += __shfl_xor(s1, o);
+      s2 += __shfl_xor(s2, o);
+    }
+    if (c0 + ch < C && (v & 7) == 0) {
+      float* part = a.workspace + (((int64_t)n * C + c0 + ch) * gridDim.x + blockIdx.x) * 2;
+      part[0] = s1;
+      part[1] = s2;
+    }
+  }
+}
+
+// one wave per (n, group): the slab's cpg x parts partials are contiguous, channel-major; lane l
+// takes items l, l + 64, ..., then the xor tree.  {m1, m2} go behind the partials.
+template <bool F16>
+__global__ __launch_bounds__(64) void gn_bwd_fold_kernel(p2p_group_norm_bwd_args a, int parts) {
+  const int G = a.groups, C = a.channels, cpg = C / G;
+  const int n = blockIdx.x / G, g = blockIdx.x - n * G;
+  const float* part = a.workspace + ((int64_t)n * C + g * cpg) * parts * 2;
+  const uint16_t* gamma = static_cast<const uint16_t*>(a.gamma) + g * cpg;
+  const int items = cpg * parts;
+  float s1 = 0.f, s2 = 0.f;
+  for (int i = threadIdx.x; i < items; i += 64) {
+    const float gm = ld16<F16>(gamma[i / parts]);
+    s1 += gm * part[2 * i];
+    s2 += gm * part[2 * i + 1];
+  }
+  for (int o = 32; o; o >>= 1) {
+    s1 += __shfl_xor(s1, o);
+    s2 += __shfl_xor(s2, o);
+  }
+  if (threadIdx.x == 0) {
+    const float inv_l = 1.f / ((float)cpg * (float)a.hw);
+    float* m = a.workspace + (int64_t)a.n * C * parts * 2 + 2 * (int64_t)blockIdx.x;
+    m[0] = s1 * inv_l;
+    m[1] = s2 * inv_l;
+  }
+}
+
+template <bool F16, bool SILU>
+__global__ __launch_bounds__(256) void gn_bwd_apply_nchw_kernel(p2p_group_norm_bwd_args a, int64_t n_vec,
+                                                                const float* means) {
+  const int64_t iv = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (iv >= n_vec) return;
+  const int hwv = a.hw >> 3;
+  const int64_t row = iv / hwv;
+  const int n = (int)(row / a.channels), c = (int)(row - (int64_t)n * a.channels);
+  const ChanCoef k = chan_coef<F16>(a, n, c);
+  const float* m = means + 2 * (n * a.groups + c / (a.channels / a.groups));
+  static_cast<u16x8_t*>(a.dx)[iv] = gn_bwd_dx8<F16, SILU>(static_cast<const u16x8_t*>(a.x)[iv],
+                                                           static_cast<const u16x8_t*>(a.dy)[iv], k, m[0], m[1]);
+}
+
+template <bool F16, bool SILU>
+__global__ __launch_bounds__(256) void gn_bwd_apply_tok_kernel(p2p_group_norm_bwd_args a, const float* means) {
+  __shared__ __attribute__((aligned(16))) uint16_t tile[kTile * kTileLd];   // [pixel][channel]
+  const int p0 = blockIdx.x * kTile, c0 = blockIdx.y * kTile, n = blockIdx.z;
+  const int C = a.channels, hw = a.hw;
+  const uint16_t* dy = static_cast<const uint16_t*>(a.dy) + (int64_t)n * hw * C;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = threadIdx.x + k * 256;
+    const int p = v >> 3, ch = (v & 7) * 8;
+    if (c0 + ch < C && p0 + p < hw)
+      *reinterpret_cast<u16x8_t*>(&tile[p * kTileLd + ch]) =
+          *reinterpret_cast<const u16x8_t*>(dy + (int64_t)(p0 + p) * C + c0 + ch);
+  }
+  __syncthreads();
+  const int64_t base = (int64_t)n * C * hw;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = threadIdx.x + k * 256;
+    const int ch = v >> 3, p = (v & 7) * 8;
+    if (c0 + ch < C && p0 + p < hw) {
+      const int c = c0 + ch;
+      const ChanCoef kc = chan_coef<F16>(a, n, c);
+      const float* m = means + 2 * (n * a.groups + c / (C / a.groups));
+      const int64_t off = base + (int64_t)c * hw + p0 + p;
+      const u16x8_t vx = *reinterpret_cast<const u16x8_t*>(static_cast<const uint16_t*>(a.x) + off);
+      u16x8_t vdy;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vdy[j] = tile[(p + j) * kTileLd + ch];
+      *reinterpret_cast<u16x8_t*>(static_cast<uint16_t*>(a.dx) + off) = gn_bwd_dx8<F16, SILU>(vx, vdy, kc, m[0], m[1]);
+    }
+  }
+}
+
+// din[m, j] = dout[m, j] * gelu(gate), din[m, d + j] = dout[m, j] * h * (Phi(gate) + gate * phi(gate))
+template <bool F16>
+__global__ __launch_bounds__(256) void geglu_bwd_kernel(p2p_geglu_bwd_args a, int64_t n_vec) {
+  const int64_t iv = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (iv >= n_vec) return;
+  const int dv = a.d >> 3;
+  const int64_t m = iv / dv;
+  const int j = (int)(iv - m * dv) * 8;
+  const uint16_t* row = static_cast<const uint16_t*>(a.in) + m * a.in_row_stride;
+  const u16x8_t h = *reinterpret_cast<const u16x8_t*>(row + j);
+  const u16x8_t g = *reinterpret_cast<const u16x8_t*>(row + a.d + j);
+  const u16x8_t dy = *reinterpret_cast<const u16x8_t*>(static_cast<const uint16_t*>(a.dout) + m * a.d + j);
+  u16x8_t oh, og;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float gate = ld16<F16>(g[i]), d = ld16<F16>(dy[i]);
+    const float cdf = 0.5f * (1.f + erff(gate * 0.70710678118654752f));
+    const float pdf = 0.39894228040143268f * __expf(-0.5f * gate * gate);
+    oh[i] = st16<F16>(d * (gate * cdf));
+    og[i] = st16<F16>(d * ld16<F16>(h[i]) * (cdf + gate * pdf));
+  }
+  uint16_t* out = static_cast<uint16_t*>(a.din) + m * 2 * a.d;
+  *reinterpret_cast<u16x8_t*>(out + j) = oh;
+  *reinterpret_cast<u16x8_t*>(out + a.d + j) = og;
+}
+
+// dst[n, hw, C] = src[n, C, hw]: gn_apply_tok_kernel's transpose without the arithmetic
+__global__ __launch_bounds__(256) void nchw_to_tokens_kernel(p2p_nchw_to_tokens_args a) {
+  __shared__ __attribute__((aligned(16))) uint16_t tile[kTile * kTileLd];   // [pixel][channel]
+  const int p0 = blockIdx.x * kTile, c0 = blockIdx.y * kTile, n = blockIdx.z;
+  const int C = a.channels, hw = a.hw;
+  const uint16_t* src = static_cast<const uint16_t*>(a.src) + (int64_t)n * C * hw;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = threadIdx.x + k * 256;
+    const int ch = v >> 3, p = (v & 7) * 8;
+    if (c0 + ch < C && p0 + p < hw) {
+      const u16x8_t in = *reinterpret_cast<const u16x8_t*>(src + (int64_t)(c0 + ch) * hw + p0 + p);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) tile[(p + j) * kTileLd + ch] = in[j];
+    }
+  }
+  __syncthreads();
+  uint16_t* dst = static_cast<uint16_t*>(a.dst) + (int64_t)n * hw * C;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int v = threadIdx.x + k * 256;
+    const int p = v >> 3, ch = (v & 7) * 8;
+    if (c0 + ch < C && p0 + p < hw)
+      *reinterpret_cast<u16x8_t*>(dst + (int64_t)(p0 + p) * C + c0 + ch) =
+          *reinterpret_cast<const u16x8_t*>(&tile[p * kTileLd + ch]);
+  }
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool io16(int dtype) { return dtype == P2P_DTYPE_BF16 || dtype == P2P_DTYPE_F16; }
 
@@ -368,7 +630,81 @@ void launch_bias_residual(const p2p_bias_residual_args& a, hipStream_t st) {
   }
 }
 
+static_assert(kTile == kGnBwdTile, "gn_bwd_workspace_floats counts the token-major partials by this tile");
+
+template <bool F16, bool SILU>
+void launch_group_norm_bwd(const p2p_group_norm_bwd_args& a, hipStream_t st) {
+  const int64_t rows = (int64_t)a.n * a.channels;
+  const dim3 tiles((a.hw + kTile - 1) / kTile, (a.channels + kTile - 1) / kTile, a.n);
+  const bool tok = a.dy_layout == P2P_LAYOUT_TOKENS;
+  const int parts = tok ? (int)tiles.x : 1;
+  if (tok) {
+    launch_kernel((gn_bwd_reduce_tok_kernel<F16, SILU>), tiles, dim3(256), 0, st, a);
+  } else if (a.hw >= kGnBwdWideRow) {
+    launch_kernel((gn_bwd_reduce_nchw_kernel<F16, SILU, 256>), dim3((unsigned)rows), dim3(256), 0, st, a);
+  } else {
+    launch_kernel((gn_bwd_reduce_nchw_kernel<F16, SILU, 64>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a);
+  }
+  launch_kernel(gn_bwd_fold_kernel<F16>, dim3((unsigned)(a.n * a.groups)), dim3(64), 0, st, a, parts);
+  const float* means = a.workspace + rows * parts * 2;
+  if (tok) {
+    launch_kernel((gn_bwd_apply_tok_kernel<F16, SILU>), tiles, dim3(256), 0, st, a, means);
+  } else {
+    const int64_t n_vec = rows * a.hw / 8;
+    launch_kernel((gn_bwd_apply_nchw_kernel<F16, SILU>), dim3((unsigned)((n_vec + 255) / 256)), dim3(256), 0, st, a,
+                  n_vec, means);
+  }
+}
+
 }  // namespace
+
+int run_group_norm_bwd(const p2p_group_norm_bwd_args& a, hipStream_t st) {
+  if (!a.x || !a.gamma || !a.beta || !a.dy || !a.stats || !a.dx || !a.workspace) return P2P_E_ARG;
+  if (a.n < 1 || a.channels < 1 || a.hw < 1 || a.groups < 1 || a.channels % a.groups) return P2P_E_ARG;
+  if (a.n > 65535 || a.channels > 65535 * kTile || (int64_t)a.n * a.channels > INT32_MAX / 2) return P2P_E_ARG;
+  // the split statistics' slabs are not served (nor is anything the 32-bit grids could not index)
+  if ((int64_t)(a.channels / a.groups) * a.hw >= kGnStatsSplit) return P2P_E_ARG;
+  if ((int64_t)a.n * a.channels * a.hw / 8 / 256 >= INT32_MAX) return P2P_E_ARG;
+  if (a.chan_add && a.chan_add_stride != 0 && a.chan_add_stride != a.channels) return P2P_E_ARG;
+  if (a.act != P2P_ACT_NONE && a.act != P2P_ACT_SILU) return P2P_E_ARG;
+  if (a.dy_layout != P2P_LAYOUT_NCHW && a.dy_layout != P2P_LAYOUT_TOKENS) return P2P_E_ARG;
+  if (!io16(a.dtype)) return P2P_E_DTYPE;
+  if (a.hw % 8 || (a.dy_layout == P2P_LAYOUT_TOKENS && a.channels % 8)) return P2P_E_ALIGN;
+  if (!aligned16(a.x) || !aligned16(a.dy) || !aligned16(a.dx)) return P2P_E_ALIGN;
+  if (((uintptr_t)a.stats & 3) || ((uintptr_t)a.workspace & 3)) return P2P_E_ALIGN;
+  const bool f16 = a.dtype == P2P_DTYPE_F16, act = a.act == P2P_ACT_SILU;
+  if (f16 && act) launch_group_norm_bwd<true, true>(a, st);
+  else if (f16) launch_group_norm_bwd<true, false>(a, st);
+  else if (act) launch_group_norm_bwd<false, true>(a, st);
+  else launch_group_norm_bwd<false, false>(a, st);
+  return (int)hipGetLastError();
+}
+
+int run_geglu_bwd(const p2p_geglu_bwd_args& a, hipStream_t st) {
+  if (!a.in || !a.dout || !a.din) return P2P_E_ARG;
+  if (a.rows < 1 || a.d < 1 || a.in_row_stride < 2 * (int64_t)a.d) return P2P_E_ARG;
+  if (!io16(a.dtype)) return P2P_E_DTYPE;
+  if (a.d % 8 || a.in_row_stride % 8) return P2P_E_ALIGN;
+  if (!aligned16(a.in) || !aligned16(a.dout) || !aligned16(a.din)) return P2P_E_ALIGN;
+  const int64_t n_vec = (int64_t)a.rows * (a.d / 8);
+  if ((n_vec + 255) / 256 > INT32_MAX) return P2P_E_ARG;
+  const dim3 grid((unsigned)((n_vec + 255) / 256));
+  if (a.dtype == P2P_DTYPE_F16) launch_kernel(geglu_bwd_kernel<true>, grid, dim3(256), 0, st, a, n_vec);
+  else launch_kernel(geglu_bwd_kernel<false>, grid, dim3(256), 0, st, a, n_vec);
+  return (int)hipGetLastError();
+}
+
+int run_nchw_to_tokens(const p2p_nchw_to_tokens_args& a, hipStream_t st) {
+  if (!a.src || !a.dst) return P2P_E_ARG;
+  if (a.n < 1 || a.channels < 1 || a.hw < 1 || a.n > 65535) return P2P_E_ARG;
+  if (!io16(a.dtype)) return P2P_E_DTYPE;
+  if (a.hw % 8 || a.channels % 8) return P2P_E_ALIGN;
+  if (!aligned16(a.src) || !aligned16(a.dst)) return P2P_E_ALIGN;
+  const dim3 grid((a.hw + kTile - 1) / kTile, (a.channels + kTile - 1) / kTile, a.n);
+  if (grid.y > 65535) return P2P_E_ARG;
+  launch_kernel(nchw_to_tokens_kernel, grid, dim3(256), 0, st, a);
+  return (int)hipGetLastError();
+}
 
 int run_group_norm(const p2p_group_norm_args& a, hipStream_t st) {
   if (!a.x || !a.gamma || !a.beta || !a.y || !a.stats) return P2P_E_ARG;

@@ -134,6 +134,30 @@ class GegluArgs(ctypes.Structure):
     ]
 
 
+class GroupNormBwdArgs(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("chan_add", ctypes.c_void_p), ("chan_add_stride", ctypes.c_int64),
+        ("chan_bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+        ("dy", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("n", ctypes.c_int32), ("channels", ctypes.c_int32), ("hw", ctypes.c_int32), ("groups", ctypes.c_int32),
+        ("act", ctypes.c_int32), ("dy_layout", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
+class GegluBwdArgs(ctypes.Structure):
+    _fields_ = [
+        ("inp", ctypes.c_void_p), ("dout", ctypes.c_void_p), ("din", ctypes.c_void_p),
+        ("in_row_stride", ctypes.c_int64), ("rows", ctypes.c_int32), ("d", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
+class NchwToTokensArgs(ctypes.Structure):
+    _fields_ = [
+        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n", ctypes.c_int32), ("channels", ctypes.c_int32),
+        ("hw", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
 class LayerNormArgs(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("add", ctypes.c_void_p), ("add_bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
@@ -222,7 +246,8 @@ def lib():
         # every export returns int, but for these
         other = {"p2p_error_string": ctypes.c_char_p, "p2p_source_hash": ctypes.c_char_p,
                  "p2p_self_attn_kernel": ctypes.c_char_p, "p2p_cross_attn_kernel": ctypes.c_char_p,
-                 "p2p_attn_bwd_workspace": ctypes.c_int64, "p2p_group_norm_stats_floats": ctypes.c_int64}
+                 "p2p_attn_bwd_workspace": ctypes.c_int64, "p2p_group_norm_stats_floats": ctypes.c_int64,
+                 "p2p_group_norm_bwd_workspace_floats": ctypes.c_int64}
         for fn in EXPORTED_SYMBOLS:
             getattr(L, fn).restype = other.get(fn, ctypes.c_int)
         L.p2p_error_string.argtypes = [ctypes.c_int]
@@ -243,6 +268,10 @@ def lib():
         L.p2p_group_norm_stats_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_bias_residual.argtypes = [ctypes.POINTER(BiasResidualArgs), vp]
         L.p2p_geglu.argtypes = [ctypes.POINTER(GegluArgs), vp]
+        L.p2p_group_norm_bwd.argtypes = [ctypes.POINTER(GroupNormBwdArgs), vp]
+        L.p2p_group_norm_bwd_workspace_floats.argtypes = [i32, i32, i32, i32]
+        L.p2p_geglu_bwd.argtypes = [ctypes.POINTER(GegluBwdArgs), vp]
+        L.p2p_nchw_to_tokens.argtypes = [ctypes.POINTER(NchwToTokensArgs), vp]
         L.p2p_causal_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp]
         L.p2p_layer_norm.argtypes = [ctypes.POINTER(LayerNormArgs), vp]
         L.p2p_bias_quick_gelu.argtypes = [ctypes.POINTER(BiasActArgs), vp]
@@ -284,7 +313,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_self_attn_kernel", "p2p_cross_attn_kernel", "p2p_plms_step", "p2p_image_u8",
                     "p2p_image_to_model", "p2p_group_norm_stats_floats", "p2p_causal_attn_fwd", "p2p_layer_norm",
                     "p2p_bias_quick_gelu", "p2p_text_attn_fwd", "p2p_bias_gelu", "p2p_maps_aggregate",
-                    "p2p_map_panels", "p2p_null_loss", "p2p_null_adam")
+                    "p2p_map_panels", "p2p_null_loss", "p2p_null_adam", "p2p_group_norm_bwd",
+                    "p2p_group_norm_bwd_workspace_floats", "p2p_geglu_bwd", "p2p_nchw_to_tokens")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -764,9 +794,11 @@ def _vec(t: Optional[torch.Tensor], like: torch.Tensor, numel: int):
 
 
 def group_norm(x, gamma, beta, groups: int, eps: float, silu: bool = False, tokens: bool = False,
-               chan_add=None, chan_bias=None):
+               chan_add=None, chan_bias=None, return_stats: bool = False):
     """act(GroupNorm(x + chan_add + chan_bias) * gamma + beta) (p2p_group_norm).  x: [N, C, H, W];
-    chan_add: [N, C] or [C]; chan_bias: [C]; returns [N, C, H, W], or [N, H*W, C] with ``tokens``."""
+    chan_add: [N, C] or [C]; chan_bias: [C]; returns [N, C, H, W], or [N, H*W, C] with ``tokens``.
+    With ``return_stats`` it returns (y, stats): the f32 workspace whose first N * groups * 2
+    elements are the {mean, rstd} pairs, which group_norm_bwd reads."""
     _require_cuda(x, gamma, beta, chan_add, chan_bias)
     if x.dim() != 4 or not x.is_contiguous():
         return None
@@ -792,7 +824,44 @@ def group_norm(x, gamma, beta, groups: int, eps: float, silu: bool = False, toke
     a.act = ACT_SILU if silu else ACT_NONE
     a.y_layout = LAYOUT_TOKENS if tokens else LAYOUT_NCHW
     a.dtype = _glue_dtype(x)
-    return y if _glue_rc(lib().p2p_group_norm(ctypes.byref(a), _stream(x.device)), "p2p_group_norm") else None
+    if not _glue_rc(lib().p2p_group_norm(ctypes.byref(a), _stream(x.device)), "p2p_group_norm"):
+        return None
+    return (y, stats) if return_stats else y
+
+
+def group_norm_bwd(dy, x, stats, gamma, beta, groups: int, silu: bool = False, tokens: bool = False,
+                   chan_add=None, chan_bias=None):
+    """The gradient of group_norm with respect to x (p2p_group_norm_bwd) from its inputs, the
+    ``stats`` it returned and ``dy`` (dense, in the layout of the forward's output).  A shape the
+    library does not serve raises: the caller decides that before the forward."""
+    _require_cuda(dy, x, stats, gamma, beta, chan_add, chan_bias)
+    N, C, H, W = x.shape
+    if not x.is_contiguous() or not dy.is_contiguous() or dy.dtype != x.dtype or \
+            tuple(dy.shape) != ((N, H * W, C) if tokens else (N, C, H, W)):
+        raise HipError(f"group_norm_bwd: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
+    if stats.dtype != torch.float32 or not stats.is_contiguous() or stats.numel() < N * int(groups) * 2:
+        raise HipError("group_norm_bwd: stats must be the forward's f32 workspace")
+    a = GroupNormBwdArgs()
+    a.x, a.dy, a.stats = x.data_ptr(), dy.data_ptr(), stats.data_ptr()
+    if chan_add is not None:
+        per_n = chan_add.dim() == 2
+        _vec(chan_add, x, N * C if per_n else C)
+        a.chan_add, a.chan_add_stride = chan_add.data_ptr(), C if per_n else 0
+    if chan_bias is not None:
+        a.chan_bias = _vec(chan_bias, x, C).data_ptr()
+    a.gamma, a.beta = _vec(gamma, x, C).data_ptr(), _vec(beta, x, C).data_ptr()
+    n_ws = int(lib().p2p_group_norm_bwd_workspace_floats(N, C, H * W, int(groups)))
+    if n_ws < 1:
+        raise HipError(f"group_norm_bwd: {C} channels in {groups} groups")
+    ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x)
+    a.dx, a.workspace = dx.data_ptr(), ws.data_ptr()
+    a.n, a.channels, a.hw, a.groups = N, C, H * W, int(groups)
+    a.act = ACT_SILU if silu else ACT_NONE
+    a.dy_layout = LAYOUT_TOKENS if tokens else LAYOUT_NCHW
+    a.dtype = _glue_dtype(x)
+    _check(lib().p2p_group_norm_bwd(ctypes.byref(a), _stream(x.device)), "p2p_group_norm_bwd")
+    return dx
 
 
 def bias_residual(a_nchw, b, bias=None, bias2=None, tokens: bool = False):
@@ -833,6 +902,42 @@ def geglu(x):
     g.rows, g.d = x2.shape[0], D
     g.dtype = _glue_dtype(x)
     return out if _glue_rc(lib().p2p_geglu(ctypes.byref(g), _stream(x.device)), "p2p_geglu") else None
+
+
+def geglu_bwd(dout, x):
+    """The gradient of geglu with respect to its input x [..., 2D] (p2p_geglu_bwd), dense in x's
+    shape, from ``dout`` [..., D] (dense).  Unsupported raises."""
+    _require_cuda(dout, x)
+    D = x.shape[-1] // 2
+    x2 = x.reshape(-1, x.shape[-1])
+    if x.shape[-1] != 2 * D or x2.stride(-1) != 1 or x2.data_ptr() != x.data_ptr():
+        raise HipError("geglu_bwd: the input must be the forward's (rows of 2 D elements, unit last stride)")
+    if not dout.is_contiguous() or dout.dtype != x.dtype or tuple(dout.shape) != tuple(x.shape[:-1]) + (D,):
+        raise HipError(f"geglu_bwd: dout {tuple(dout.shape)} {dout.dtype} does not match x {tuple(x.shape)} {x.dtype}")
+    g = GegluBwdArgs()
+    din = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    g.inp, g.dout, g.din = x2.data_ptr(), dout.data_ptr(), din.data_ptr()
+    g.in_row_stride = x2.stride(0) if x2.shape[0] > 1 else 2 * D
+    g.rows, g.d = x2.shape[0], D
+    g.dtype = _glue_dtype(x)
+    _check(lib().p2p_geglu_bwd(ctypes.byref(g), _stream(x.device)), "p2p_geglu_bwd")
+    return din
+
+
+def nchw_to_tokens(src):
+    """[N, C, H, W] -> [N, H*W, C] (p2p_nchw_to_tokens): permute(0, 2, 3, 1) made dense, the
+    gradient of bias_residual's token-major operand.  Unsupported raises."""
+    _require_cuda(src)
+    if src.dim() != 4 or not src.is_contiguous():
+        raise HipError("nchw_to_tokens needs a dense [N, C, H, W] tensor")
+    N, C, H, W = src.shape
+    t = NchwToTokensArgs()
+    dst = src.new_empty((N, H * W, C))
+    t.src, t.dst = src.data_ptr(), dst.data_ptr()
+    t.n, t.channels, t.hw = N, C, H * W
+    t.dtype = _glue_dtype(src)
+    _check(lib().p2p_nchw_to_tokens(ctypes.byref(t), _stream(src.device)), "p2p_nchw_to_tokens")
+    return dst
 
 
 # -- the image ends (p2p_image.hip).  As the glue above: None where the library reports the shape

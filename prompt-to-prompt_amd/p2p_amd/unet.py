@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _hip
+from . import _hip, unet_grad
 
 # The norm / activation / bias / residual / GEGLU glue between the convolutions and GEMMs runs on
 # the HIP kernels of csrc/p2p_unet.hip (A/B switch, read once: 0 = the torch lines everywhere)
@@ -30,15 +30,54 @@ FUSE_UNET = os.environ.get("P2P_FUSE_UNET", "1") != "0"
 
 def fused_glue(*tensors: torch.Tensor) -> bool:
     """Whether a module takes its fused path: inference (grad mode off) on GPU tensors in bf16 or
-    f16, and the switch on.  Everything else -- CPU, f32, null-text inversion under autograd --
-    runs the torch lines."""
+    f16, and the switch on.  Everything else -- CPU, f32, grad mode on -- runs the torch lines,
+    unless ``fused_glue_grad`` takes the call (the U-Net's modules under autograd)."""
     if not FUSE_UNET or torch.is_grad_enabled():
         return False
     return all(t.is_cuda and t.dtype in (torch.bfloat16, torch.float16) for t in tensors)
 
 
+# Under autograd the same glue runs with the HIP backward of its kernels (unet_grad.py): null-text
+# inversion's inner steps.  A/B switch, read once: 0 = the torch lines whenever grad mode is on
+FUSE_UNET_GRAD = os.environ.get("P2P_FUSE_UNET_GRAD", "1") != "0"
+GN_SLAB_LIMIT = 262144      # kGnStatsSplit (csrc/p2p_kernels.h): the backward serves slabs below it
+
+
+def fused_glue_grad(*tensors: torch.Tensor, params=(), norms=(), tokens: bool = False) -> bool:
+    """Whether a module takes its fused path under autograd: grad mode on, both switches on,
+    ``tensors`` (the activations the glue differentiates) and ``params`` (the module's parameters and
+    per-channel adds; None entries are skipped) on the GPU in bf16 or f16, none of ``params``
+    requiring grad -- the kernels compute no gradient for them -- and sizes the backward serves,
+    decided here from the sizes alone: a 4-D activation needs H * W % 8 == 0 (and C % 8 == 0 where
+    the glue goes through ``tokens``) and, for every GroupNorm of ``norms``, a (sample, group) slab
+    below GN_SLAB_LIMIT elements; any other activation is GEGLU's [..., 2 D] with D % 8 == 0 and a
+    row stride % 8 == 0."""
+    if not (FUSE_UNET and FUSE_UNET_GRAD) or not torch.is_grad_enabled():
+        return False
+    params = [p for p in params if p is not None]
+    if not all(t.is_cuda and t.dtype in (torch.bfloat16, torch.float16) for t in (*tensors, *params)):
+        return False
+    if any(p.requires_grad for p in params):
+        return False
+    for t in tensors:
+        if t.dim() == 4:
+            hw = t.shape[2] * t.shape[3]
+            if hw % 8 or (tokens and t.shape[1] % 8):
+                return False
+            if any(nm.num_channels // nm.num_groups * hw >= GN_SLAB_LIMIT for nm in norms):
+                return False
+        elif t.shape[-1] % 16 or (t.dim() > 1 and t.stride(-2) % 8):
+            return False
+    return True
+
+
 def _norm_act(norm: nn.GroupNorm, x, **kw):
-    return _hip.group_norm(x, norm.weight, norm.bias, norm.num_groups, norm.eps, **kw)
+    glue = unet_grad if torch.is_grad_enabled() else _hip
+    return glue.group_norm(x, norm.weight, norm.bias, norm.num_groups, norm.eps, **kw)
+
+
+def _bias_residual(*args, **kw):
+    return (unet_grad if torch.is_grad_enabled() else _hip).bias_residual(*args, **kw)
 
 
 class CrossAttention(nn.Module):
@@ -79,8 +118,8 @@ class GEGLU(nn.Module):
 
     def forward(self, x):
         p = self.proj(x)
-        if fused_glue(p):
-            out = _hip.geglu(p)
+        if fused_glue(p) or fused_glue_grad(p):
+            out = (unet_grad if torch.is_grad_enabled() else _hip).geglu(p)
             if out is not None:
                 return out
         h, gate = p.chunk(2, dim=-1)
@@ -134,12 +173,13 @@ class Transformer2DModel(nn.Module):
         for blk in self.transformer_blocks:
             t = blk(t, context=ctx)
         t = F.linear(t, po.weight.view(po.out_channels, po.in_channels), po.bias)
-        out = _hip.bias_residual(x, t, tokens=True)
+        out = _bias_residual(x, t, tokens=True)
         # (the blocks have run, controllers included: finish here rather than run them again)
         return out if out is not None else t.reshape(b, h, w, c).permute(0, 3, 1, 2) + x
 
     def forward(self, x, encoder_hidden_states=None):
-        if fused_glue(x, self.proj_in.weight):
+        if fused_glue(x, self.proj_in.weight) or fused_glue_grad(
+                x, params=(self.norm.weight, self.norm.bias, self.proj_in.weight), norms=(self.norm,), tokens=True):
             out = self._forward_fused(x, encoder_hidden_states)
             if out is not None:
                 return out
@@ -179,11 +219,17 @@ class ResnetBlock2D(nn.Module):
             return None
         h = c2._conv_forward(h, c2.weight, None)
         if sc is not None:
-            return _hip.bias_residual(sc._conv_forward(x, sc.weight, None), h, c2.bias, sc.bias)
-        return _hip.bias_residual(x, h, c2.bias)
+            return _bias_residual(sc._conv_forward(x, sc.weight, None), h, c2.bias, sc.bias)
+        return _bias_residual(x, h, c2.bias)
+
+    def _glue_params(self, temb):
+        """The module's parameters and the time embedding: the glue's backward leaves the norms'
+        affine, the biases and the per-channel add without a gradient."""
+        return (*self.parameters(), temb)
 
     def forward(self, x, temb=None):
-        if fused_glue(x, self.conv1.weight, *(() if temb is None else (temb,))):
+        if fused_glue(x, self.conv1.weight, *(() if temb is None else (temb,))) or fused_glue_grad(
+                x, params=self._glue_params(temb), norms=(self.norm1, self.norm2)):
             out = self._forward_fused(x, temb)
             if out is not None:
                 return out
@@ -382,6 +428,8 @@ class UNet2DConditionModel(nn.Module):
             n = len(blk.resnets)
             res, skips = skips[-n:], skips[:-n]
             x = blk(x, emb, res, ctx)
-        h = _norm_act(self.conv_norm_out, x, silu=True) if fused_glue(x) else None
+        nout = self.conv_norm_out
+        fused = fused_glue(x) or fused_glue_grad(x, params=(nout.weight, nout.bias), norms=(nout,))
+        h = _norm_act(nout, x, silu=True) if fused else None
         x = self.conv_out(h if h is not None else F.silu(self.conv_norm_out(x)))
         return {"sample": x}
