@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import abc
 from collections import defaultdict
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -66,16 +66,25 @@ class NotFusable(Exception):
 
 
 # ============================================================================ LocalBlend
-def fused_local_blend(x_t, attention_store, alpha_flat, sub_flat, th_pool, th_sub):
-    """LocalBlend on the running-sum store with the HIP blend kernels (returns a new x_t)."""
+def _blend_maps(attention_store, alpha_flat, workspace=True):
+    """The five 16x16 cross maps LocalBlend reads (main.py:37-38) as dense f32, their heads per
+    prompt and (``workspace``) the word-sum workspace p2p_localblend fills from them."""
     maps = list(attention_store["down_cross"][2:4]) + list(attention_store["up_cross"][:3])
     B = alpha_flat.shape[0]
     if len(maps) != 5:
         raise ValueError(f"LocalBlend needs 2 down and 3 up 16x16 cross maps, store has {len(maps)}")
     heads = maps[0].shape[0] // B
     maps = [m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous() for m in maps]
+    if not workspace:
+        return maps, heads, None
+    return maps, heads, torch.empty(B * 2 * len(maps) * heads * maps[0].shape[1], dtype=torch.float32,
+                                    device=maps[0].device)
+
+
+def fused_local_blend(x_t, attention_store, alpha_flat, sub_flat, th_pool, th_sub):
+    """LocalBlend on the running-sum store with the HIP blend kernels (returns a new x_t)."""
+    maps, heads, ws = _blend_maps(attention_store, alpha_flat)
     out = x_t.to(torch.float32).contiguous().clone()
-    ws = torch.empty(B * 2 * len(maps) * heads * maps[0].shape[1], dtype=torch.float32, device=out.device)
     _hip.localblend(maps, heads, alpha_flat, sub_flat, th_pool, th_sub, out, ws)
     return out.to(x_t.dtype)
 
@@ -108,6 +117,14 @@ def as_mask(m):
     return m.materialize() if isinstance(m, FoldedBlendMask) else m
 
 
+class StepMask(NamedTuple):
+    """What fused_step_mask()'s mask_fn(size) returns: per prompt group None (no blend this step), a
+    uint8 mask [B, H, W] or a FoldedBlendMask; group_size 0 = a single controller (one group, the
+    whole batch).  ptp_utils._launch_latent_step turns it into the latent step's arguments."""
+    entries: list
+    group_size: int
+
+
 def group_mask_tensor(masks, B, size):
     """Per-group step masks (None = the group does not blend) as the mask-reading latent step's
     (mask [G*B, H, W] uint8, group size, groups that blend [G] uint8) triple."""
@@ -128,17 +145,11 @@ def fused_blend_mask(attention_store, alpha_flat, sub_flat, th_pool, th_sub, siz
     sums [B, 2, 5 * heads, 256] that the cross-attention store epilogue accumulated
     (AttentionControlEdit._blend_fold) -- then the 12.6 MB of maps are not re-read, and the mask
     is returned as a FoldedBlendMask that p2p_latent_step builds in the same launch."""
-    maps = list(attention_store["down_cross"][2:4]) + list(attention_store["up_cross"][:3])
-    B = alpha_flat.shape[0]
-    if len(maps) != 5:
-        raise ValueError(f"LocalBlend needs 2 down and 3 up 16x16 cross maps, store has {len(maps)}")
-    heads = maps[0].shape[0] // B
-    dev = maps[0].device
     if folded is not None:
+        maps, heads, _ = _blend_maps(attention_store, alpha_flat, workspace=False)
         return FoldedBlendMask(maps, heads, alpha_flat, sub_flat, th_pool, th_sub, size, folded)
-    mask = torch.empty(B, *size, dtype=torch.uint8, device=dev)
-    maps = [m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous() for m in maps]
-    ws = torch.empty(B * 2 * len(maps) * heads * maps[0].shape[1], dtype=torch.float32, device=dev)
+    maps, heads, ws = _blend_maps(attention_store, alpha_flat)
+    mask = torch.empty(alpha_flat.shape[0], *size, dtype=torch.uint8, device=ws.device)
     _hip.localblend(maps, heads, alpha_flat, sub_flat, th_pool, th_sub, None, ws, mask_out=mask)
     return mask
 
@@ -201,13 +212,18 @@ class AttentionControl(abc.ABC):
 
     def fused_step_mask(self):
         """Fused latent-step protocol (ptp_utils.diffusion_step): (True, mask_fn) when this
-        step's step_callback is this library's own -- mask_fn(size) then has the callback's
-        side effects and returns the LocalBlend mask or None -- else (False, None)."""
+        step's step_callback is this library's own -- mask_fn (None: nothing to do) then has the
+        callback's side effects and returns the step's StepMask -- else (False, None)."""
         if not _owned(self, "step_callback"):
             return False, None
-        return True, self._step_mask_fn()
+        try:
+            entry_fn = self._step_mask_entry()
+        except NotFusable:
+            return False, None
+        return True, (None if entry_fn is None else lambda size: StepMask([entry_fn(size)], 0))
 
-    def _step_mask_fn(self):
+    def _step_mask_entry(self):
+        """None, or fn(size) -> this controller's StepMask entry."""
         return None
 
     def between_steps(self):
@@ -237,15 +253,20 @@ class AttentionControl(abc.ABC):
             self.cur_att_layer = 0
             self.cur_step += 1
             self.between_steps()
+            self._fused_calls = defaultdict(int)
 
     def reset(self):
         self.cur_step = 0
         self.cur_att_layer = 0
+        self._fused_calls, self._fused_sums = defaultdict(int), {}
 
     def __init__(self):
         self.cur_step = 0
         self.num_att_layers = -1
         self.cur_att_layer = 0
+        # the fused store's bookkeeping (_fused_attention): stored calls so far this step per
+        # "<place>_<kind>" key, and the running-sum tensor of each (key, call)
+        self._fused_calls, self._fused_sums = defaultdict(int), {}
 
     # ------------------------------------------------------------------ fused protocol
     def fused_supported(self) -> bool:
@@ -282,6 +303,97 @@ class AttentionControl(abc.ABC):
 
     def _cond_start(self, n_batch: int) -> int:
         return 0 if _low_resource() else n_batch // 2
+
+    # What a controller contributes to its prompt group of a fused call.  A plain controller
+    # contributes nothing; AttentionStore adds its stores (step_store, attention_store,
+    # store_self_maps), AttentionControlEdit its edit (batch_size, _cross_alpha, _cross_step,
+    # _blend_fold, _injects_source).  GroupBatch drives its members through these and
+    # _advance_layer only.
+    def _cross_alpha(self):
+        """This step's cross_replace_alpha row; None: no cross-attention edit."""
+        return None
+
+    def _injects_source(self, K: int) -> bool:
+        """Whether this step's self-attention over K keys gives the edits the source's Q and K."""
+        return False
+
+    def _fused_attention(self, members, group_size, q, k, v, heads, scale, is_cross, place_in_unet):
+        """ONE kernel launch for the prompt groups that share this U-Net call: ``members`` holds one
+        controller per group, each owning ``group_size`` prompts of the conditional half -- or, with
+        group_size 0, the single controller ``[self]`` whose group is the conditional half whatever
+        its size.  Translates the members' state into the kernels' terms: the AttentionStore target
+        (allocated on the first step, accumulated into afterwards; every member's step_store gets its
+        view of the one running-sum tensor per layer) and slots, the p2p_group tuples of
+        _hip.cross_attn, the qk_src remap of _hip.self_attn.  ``self`` keeps the store bookkeeping."""
+        N, P, K = q.shape[0], q.shape[1], k.shape[1]
+        batched = group_size > 0
+        if batched:
+            B, n0 = group_size, len(members) * group_size
+            if N != 2 * n0:
+                raise ValueError(f"GroupBatch of {len(members)} x {B} prompts got a U-Net batch of {N}")
+        else:
+            n0 = self._cond_start(N)
+            B = N - n0
+        for m in members:
+            if getattr(m, "batch_size", B) != B:
+                raise ValueError(f"controller built for {m.batch_size} prompts got a batch of {B}")
+        cross = is_cross and K <= _hip.MAX_KEYS_CROSS
+        edits = [None] * len(members)       # per member None or its cross edit (alpha row, program, hints)
+        if is_cross:
+            alphas = [m._cross_alpha() for m in members]
+            fit = cross and all(a is None or (a.shape[-1] == K and a.device == q.device) for a in alphas)
+            if not batched and alphas[0] is not None and not fit:
+                raise NotFusable        # a single edit controller falls back to the materialised protocol
+            if cross and not fit:
+                raise ValueError("edit tables do not match this attention call")
+            if cross:   # (before the store is touched: a program the tables cannot hold raises NotFusable)
+                edits = [None if a is None else (a.contiguous(),) + m._cross_step(q.device, K)
+                         for m, a in zip(members, alphas)]
+        self_maps = {bool(m.store_self_maps) for m in members if isinstance(m, AttentionStore)}
+        if not is_cross and len(self_maps) > 1:
+            raise ValueError("GroupBatch members disagree on store_self_maps")
+        store, acc, slots, store_key = None, False, None, None
+        if self_maps and P <= MAX_STORED_QUERIES and (is_cross or True in self_maps):
+            key = f"{place_in_unet}_{'cross' if is_cross else 'self'}"
+            store_key = (key, self._fused_calls[key])
+            self._fused_calls[key] += 1
+            if len(members[0].attention_store) == 0:
+                rows = B * heads
+                store = self._fused_sums[store_key] = torch.empty(len(members) * rows, P, K, dtype=torch.float32,
+                                                                  device=q.device)
+                for g, m in enumerate(members):
+                    m.step_store[key].append(store[g * rows:(g + 1) * rows])
+            else:
+                store, acc = self._fused_sums.get(store_key), True
+                if store is None:       # this layer's sum was not made here (a materialised first step)
+                    raise NotFusable
+            slots = [-1] * n0 + [(n - n0) * heads for n in range(n0, N)]
+        out = torch.empty_like(q)
+        if not cross:
+            qk_src = None                   # (the identity)
+            for g, m in enumerate(members):
+                if not is_cross and m._injects_source(K):
+                    first = n0 + g * B      # P_edit <- P_source, V stays the edit's own
+                    qk_src = qk_src or list(range(N))
+                    qk_src[first + 1:first + B] = [first] * (B - 1)
+            _hip.self_attn(q, k, v, out, heads, scale, compute=config.COMPUTE, qk_src=qk_src, store=store,
+                           store_slot=slots, accumulate=acc)
+            return out
+        if batched or edits[0] is not None:
+            # the uncond rows ("" prompts) share their K / V: staged once per workgroup (SHARED_KV)
+            groups = [(0, n0, None, None, None, _hip.shared_kv_hint(k, v, 0, n0))] if n0 else []
+            for g, (m, edit) in enumerate(zip(members, edits)):
+                if edit is None:
+                    groups.append((n0 + g * B, B, None, None))
+                    continue
+                alpha, prog, hints = edit
+                blend = m._blend_fold(store_key, P, K, heads, q.device) if store is not None else None
+                groups.append((n0 + g * B, B, prog, alpha, blend, hints))
+        else:
+            groups = [(0, N, None, None)]       # a plain controller: one group over the whole batch
+        _hip.cross_attn(q, k, v, out, heads, scale, groups, compute=config.COMPUTE, store=store, store_slot=slots,
+                        accumulate=acc)
+        return out
 
 
 AttentionControl._P2P_LIB = True
@@ -330,7 +442,6 @@ class AttentionStore(AttentionControl):
                 for i, item in enumerate(items):
                     self.attention_store[key][i] += item
         self.step_store = self.get_empty_store()
-        self._fused_calls = defaultdict(int)
 
     def get_average_attention(self):
         def avg(item):
@@ -343,48 +454,14 @@ class AttentionStore(AttentionControl):
         super().reset()
         self.step_store = self.get_empty_store()
         self.attention_store = {}
-        self._fused_calls = defaultdict(int)
 
     def __init__(self):
         super().__init__()
         self.step_store = self.get_empty_store()
         self.attention_store = {}
-        self._fused_calls = defaultdict(int)
-
-    # ------------------------------------------------------------------ fused store
-    def _store_target(self, is_cross, place_in_unet, n_cond, heads, P, K, device):
-        """Running-sum tensor this call's maps go to, and whether to add or overwrite."""
-        if P > MAX_STORED_QUERIES or (not is_cross and not self.store_self_maps):
-            return None, False
-        key = f"{place_in_unet}_{'cross' if is_cross else 'self'}"
-        idx = self._fused_calls[key]
-        self._fused_calls[key] = idx + 1
-        self._last_store_key = (key, idx)
-        if len(self.attention_store) == 0:
-            t = torch.empty(n_cond * heads, P, K, dtype=torch.float32, device=device)
-            self.step_store[key].append(t)
-            return t, False
-        return self.attention_store[key][idx], True
-
-    def _slots(self, n_batch, n0, heads, store):
-        if store is None:
-            return None
-        return [-1] * n0 + [(n - n0) * heads for n in range(n0, n_batch)]
 
     def _fused_forward(self, q, k, v, heads, scale, is_cross, place_in_unet):
-        N, P, K = q.shape[0], q.shape[1], k.shape[1]
-        n0 = self._cond_start(N)
-        store, acc = self._store_target(is_cross, place_in_unet, N - n0, heads, P, K, q.device)
-        slots = self._slots(N, n0, heads, store)
-        out = torch.empty_like(q)
-        if is_cross and K <= _hip.MAX_KEYS_CROSS:
-            groups = [(0, N, None, None)]
-            _hip.cross_attn(q, k, v, out, heads, scale, groups, compute=config.COMPUTE, store=store,
-                            store_slot=slots, accumulate=acc)
-        else:
-            _hip.self_attn(q, k, v, out, heads, scale, compute=config.COMPUTE, store=store,
-                           store_slot=slots, accumulate=acc)
-        return out
+        return self._fused_attention([self], 0, q, k, v, heads, scale, is_cross, place_in_unet)
 
 
 AttentionStore._P2P_LIB = True
@@ -401,7 +478,7 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
             x_t = self.local_blend(x_t, self.attention_store)
         return x_t
 
-    def _step_mask_fn(self):
+    def _step_mask_entry(self):
         lb = self.local_blend
         if lb is None:
             return None
@@ -455,12 +532,6 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
         super().reset()
         self._blend_sums, self._blend_valid, self._blend_step = None, False, set()
 
-    def fused_step_mask(self):
-        try:
-            return super().fused_step_mask()
-        except NotFusable:
-            return False, None
-
     def replace_self_attention(self, attn_base, att_replace):
         if att_replace.shape[2] <= self.SELF_REPLACE_MAX_KEYS:
             return attn_base.unsqueeze(0).expand(att_replace.shape[0], *attn_base.shape)
@@ -472,6 +543,12 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
 
     def _in_self_window(self) -> bool:
         return self.num_self_replace[0] <= self.cur_step < self.num_self_replace[1]
+
+    def _injects_source(self, K):
+        return self._in_self_window() and K <= self.SELF_REPLACE_MAX_KEYS
+
+    def _cross_alpha(self):
+        return self.cross_replace_alpha[self.cur_step]
 
     def _replace_self(self, attn_base, att_replace, place_in_unet):
         return self.replace_self_attention(attn_base, att_replace)
@@ -557,37 +634,6 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
         hints = _hip.GROUP_F_R_ONLY if np.all(A == 0.0) else 0
         self._step_cache[key] = (plain, hints)
         return (None if plain else prog), hints
-
-    def _fused_forward(self, q, k, v, heads, scale, is_cross, place_in_unet):
-        N, P, K = q.shape[0], q.shape[1], k.shape[1]
-        n0 = self._cond_start(N)
-        n_cond = N - n0
-        if n_cond != self.batch_size:
-            raise ValueError(f"controller built for {self.batch_size} prompts got a batch of {n_cond}")
-        if is_cross:
-            alpha = self.cross_replace_alpha[self.cur_step]
-            if K > _hip.MAX_KEYS_CROSS or alpha.shape[-1] != K or alpha.device != q.device:
-                raise NotFusable
-            prog, hints = self._cross_step(q.device, K)
-        store, acc = self._store_target(is_cross, place_in_unet, n_cond, heads, P, K, q.device)
-        slots = self._slots(N, n0, heads, store)
-        out = torch.empty_like(q)
-        if is_cross:
-            blend = self._blend_fold(self._last_store_key, P, K, heads, q.device) if store is not None else None
-            # the uncond rows ("" prompts) share their K / V: staged once per workgroup (SHARED_KV)
-            groups = (([(0, n0, None, None, None, _hip.shared_kv_hint(k, v, 0, n0))] if n0 else [])
-                      + [(n0, n_cond, prog, alpha.contiguous(), blend, hints)])
-            _hip.cross_attn(q, k, v, out, heads, scale, groups, compute=config.COMPUTE, store=store,
-                            store_slot=slots, accumulate=acc)
-        else:
-            qk_src = None
-            if self._in_self_window() and K <= self.SELF_REPLACE_MAX_KEYS:
-                qk_src = list(range(N))
-                for n in range(n0 + 1, N):
-                    qk_src[n] = n0       # P_edit <- P_source, V stays the edit's own
-            _hip.self_attn(q, k, v, out, heads, scale, compute=config.COMPUTE, qk_src=qk_src, store=store,
-                           store_slot=slots, accumulate=acc)
-        return out
 
 
 AttentionControlEdit._P2P_LIB = True
@@ -708,11 +754,8 @@ class GroupBatch(AttentionControl):
         storing = {isinstance(m, AttentionStore) for m in self.members}
         if len(storing) != 1:
             raise ValueError("mix of storing and non-storing controllers")
-        self._storing = storing.pop()
-        if self._storing and len({bool(m.store_self_maps) for m in self.members}) != 1:
+        if storing.pop() and len({bool(m.store_self_maps) for m in self.members}) != 1:
             raise ValueError("GroupBatch members disagree on store_self_maps")
-        self._calls = defaultdict(int)
-        self._combined = defaultdict(list)
 
     # counters: the composite counts like any controller and moves every member in lockstep
     @property
@@ -728,15 +771,10 @@ class GroupBatch(AttentionControl):
     def forward(self, attn, is_cross: bool, place_in_unet: str):
         raise NotImplementedError("GroupBatch runs only on the fused kernels (no materialised protocol)")
 
-    def between_steps(self):
-        self._calls = defaultdict(int)
-
     def reset(self):
         super().reset()
         for m in getattr(self, "members", ()):
             m.reset()
-        self._calls = defaultdict(int)
-        self._combined = defaultdict(list)
 
     def step_callback(self, x_t):
         B = self.group_size
@@ -752,78 +790,14 @@ class GroupBatch(AttentionControl):
         if all(fn is None for fn in fns):
             return True, None
         B = self.group_size
-
-        def mask_fn(size):
-            masks = [fn(size) if fn is not None else None for fn in fns]
-            if all(mk is None for mk in masks):
-                return None
-            folded = [mk for mk in masks if isinstance(mk, FoldedBlendMask)]
-            if folded and len(folded) == sum(mk is not None for mk in masks) and \
-                    len({f.latent_entry()[1:] for f in folded}) == 1:
-                # every blending group folded, one threshold set: the masks are built inside
-                # p2p_latent_step (one launch per step for the whole batch)
-                return masks, B
-            return group_mask_tensor(masks, B, size)
-
-        return True, mask_fn
-
-    def _fused_forward(self, q, k, v, heads, scale, is_cross, place_in_unet):
-        if _low_resource():
-            raise ValueError("GroupBatch does not run with LOW_RESOURCE (one U-Net call per CFG half)")
-        N, P, K = q.shape[0], q.shape[1], k.shape[1]
-        B, G = self.group_size, len(self.members)
-        GB = G * B
-        if N != 2 * GB:
-            raise ValueError(f"GroupBatch of {G} x {B} prompts got a U-Net batch of {N}")
-        store, acc, slots, store_key = None, False, None, None
-        store_self = self._storing and all(m.store_self_maps for m in self.members)
-        if self._storing and not is_cross and any(m.store_self_maps for m in self.members) and not store_self:
-            raise ValueError("GroupBatch members disagree on store_self_maps")
-        if self._storing and P <= MAX_STORED_QUERIES and (is_cross or store_self):
-            key = f"{place_in_unet}_{'cross' if is_cross else 'self'}"
-            idx = self._calls[key]
-            self._calls[key] = idx + 1
-            store_key = (key, idx)
-            if len(self.members[0].attention_store) == 0:
-                store = torch.empty(GB * heads, P, K, dtype=torch.float32, device=q.device)
-                for g, m in enumerate(self.members):
-                    m.step_store[key].append(store[g * B * heads:(g + 1) * B * heads])
-                self._combined[key].append(store)
-            else:
-                store, acc = self._combined[key][idx], True
-            slots = [-1] * GB + [(n - GB) * heads for n in range(GB, N)]
-        out = torch.empty_like(q)
-        if is_cross and K <= _hip.MAX_KEYS_CROSS:
-            groups = [(0, GB, None, None, None, _hip.shared_kv_hint(k, v, 0, GB))]
-            for g, m in enumerate(self.members):
-                first = GB + g * B
-                if isinstance(m, AttentionControlEdit):
-                    alpha = m.cross_replace_alpha[m.cur_step]
-                    if alpha.shape[-1] != K or alpha.device != q.device:
-                        raise ValueError("edit tables do not match this attention call")
-                    blend = m._blend_fold(store_key, P, K, heads, q.device) if store is not None else None
-                    prog, hints = m._cross_step(q.device, K)
-                    groups.append((first, B, prog, alpha.contiguous(), blend, hints))
-                else:
-                    groups.append((first, B, None, None))
-            _hip.cross_attn(q, k, v, out, heads, scale, groups, compute=config.COMPUTE, store=store,
-                            store_slot=slots, accumulate=acc)
-        else:
-            qk_src = list(range(N))
-            for g, m in enumerate(self.members):
-                if (isinstance(m, AttentionControlEdit) and not is_cross and m._in_self_window()
-                        and K <= m.SELF_REPLACE_MAX_KEYS):
-                    src = GB + g * B
-                    for b in range(1, B):
-                        qk_src[src + b] = src
-            _hip.self_attn(q, k, v, out, heads, scale, compute=config.COMPUTE, qk_src=qk_src, store=store,
-                           store_slot=slots, accumulate=acc)
-        return out
+        return True, lambda size: StepMask([fn(size).entries[0] if fn is not None else None for fn in fns], B)
 
     def attention(self, q, k, v, heads, scale, is_cross, place_in_unet, mask=None):
         if mask is not None:
             raise ValueError("GroupBatch does not take an attention mask")
-        out = self._fused_forward(q, k, v, heads, scale, is_cross, place_in_unet)
+        if _low_resource():
+            raise ValueError("GroupBatch does not run with LOW_RESOURCE (one U-Net call per CFG half)")
+        out = self._fused_attention(self.members, self.group_size, q, k, v, heads, scale, is_cross, place_in_unet)
         for m in self.members:
             m._advance_layer()
         self._advance_layer()

@@ -112,7 +112,6 @@ def diffusion_step(model, controller, latents, context, t, guidance_scale, low_r
 
 
 def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale):
-    from . import _hip
     from .ddim import DDIMScheduler
     from .pndm import PNDMScheduler
     sched = model.scheduler
@@ -124,7 +123,6 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
         return None
     if eps is None or not eps.is_contiguous():
         eps = torch.cat([eps_u, eps_c]).contiguous()
-    from .controllers import FoldedBlendMask, group_mask_tensor
     x = latents.contiguous()
     out = torch.empty_like(x)
     plms = isinstance(sched, PNDMScheduler)
@@ -136,29 +134,43 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
         src = sched.step_source(plan, x).contiguous()
         hist, hist_out = sched.history(plan), sched.history_slot(plan, x)
     else:
-        src, hist, hist_out = x, (), None
-    mask = mask_fn(tuple(x.shape[2:])) if mask_fn is not None else None
-    group_size, group_blend, blend = 0, None, None
-    folded = mask if isinstance(mask, FoldedBlendMask) else (
-        next((m for m in mask[0] if m is not None), None) if isinstance(mask, tuple) and len(mask) == 2 else None)
+        plan, src, hist, hist_out = None, x, (), None
+    _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out)
+    if plms:
+        sched.commit(plan, hist_out, x)
+    return out
+
+
+def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out):
+    """The step's mask (mask_fn's side effects included) and the one p2p_latent_step / p2p_plms_step
+    launch (``plan``: the PLMS call's plan, None for DDIM) that reads it."""
+    from . import _hip
+    from .controllers import FoldedBlendMask, StepMask, as_mask, group_mask_tensor
+    plms = plan is not None
+    size = tuple(x.shape[2:])
+    step = mask_fn(size) if mask_fn is not None else StepMask([None], 0)
+    if not isinstance(step, StepMask):     # a controller of the caller's own may return its one entry bare
+        step = StepMask([step], 0)
+    entries, group_size = step
+    mask, group_blend, blend = None, None, None
+    blending = [e for e in entries if e is not None]
     kept = hist + ((hist_out,) if hist_out is not None else ())
-    if folded is not None and not _blend_launch_ok(src, out, eps, folded, kept):
-        # shapes the one-launch LocalBlend does not take: the mask is built by p2p_localblend and
-        # the latent step reads it (the same mask, two launches)
-        mask = folded.materialize() if isinstance(mask, FoldedBlendMask) else group_mask_tensor(
-            mask[0], mask[1], tuple(x.shape[2:]))
-    if isinstance(mask, FoldedBlendMask):  # LocalBlend built inside the latent-step launch
-        mask, blend = None, [mask.latent_entry()]
-    elif isinstance(mask, tuple) and len(mask) == 2:   # prompt-group batch, every blending group folded
-        blend = [m.latent_entry() if m is not None else None for m in mask[0]]
-        mask, group_size = None, mask[1]
-    elif isinstance(mask, tuple):          # prompt-group batch: (mask, group size, groups that blend)
-        mask, group_size, group_blend = mask
+    if not blending:
+        group_size = 0
+    elif (all(isinstance(e, FoldedBlendMask) for e in blending) and len({e.latent_entry()[1:] for e in blending}) == 1
+          and _blend_launch_ok(src, out, eps, blending[0], kept)):
+        # every blending group folded, one threshold set: the masks are built inside the latent-step
+        # launch (one launch per step for the whole batch)
+        blend = [e.latent_entry() if e is not None else None for e in entries]
+    elif group_size == 0:
+        # a mask, or shapes the one-launch LocalBlend does not take: the mask is built by
+        # p2p_localblend and the latent step reads it (the same mask, two launches)
+        mask = as_mask(entries[0])
+    else:
+        mask, group_size, group_blend = group_mask_tensor(entries, group_size, size)
     if not plms:
         return _hip.latent_step(eps, x, out, sched.prev_coeffs(t), guidance_scale, mask, group_size, group_blend, blend)
-    _hip.plms_step(eps, src, out, plan, guidance_scale, mask, group_size, group_blend, blend, hist, hist_out)
-    sched.commit(plan, hist_out, x)
-    return out
+    return _hip.plms_step(eps, src, out, plan, guidance_scale, mask, group_size, group_blend, blend, hist, hist_out)
 
 
 def _blend_launch_ok(x, out, eps, folded, more=()) -> bool:
