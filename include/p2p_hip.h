@@ -456,6 +456,52 @@ typedef struct {
 
 int p2p_nchw_to_tokens(const p2p_nchw_to_tokens_args* a, p2p_stream_t stream);
 
+/* The U-Net's time path (p2p_amd/unet.py UNet2DConditionModel.forward; additive to ABI 16), under
+ * the glue's contract: 16-bit weights and results, f32 accumulation in a fixed order, one rounding.
+ *
+ * p2p_time_embed: emb[n, :] = W2 . silu(W1 . [cos(t_n f_i), sin(t_n f_i)] + b1) + b2, the sinusoid
+ * of timestep_embedding (f_i = exp(-ln(10000) i / half), half = in_channels / 2, cosines first) with
+ * accurate cosf / sinf / expf, and TimestepEmbedding's two layers.  Nothing is rounded before emb:
+ * linear_1's output stays f32, in `workspace`.  Two launches.  Rejected before any launch: a null
+ * pointer, n outside [1, P2P_MAX_BATCH], in_channels or d outside [1, 2048], a timestep_stride
+ * other than 0 or 1 (P2P_E_ARG); in_channels % 8 or d % 8, w1 / w2 / workspace / emb off 16 bytes,
+ * timesteps off 8, a bias off 2 (P2P_E_ALIGN). */
+typedef struct {
+  const int64_t* timesteps;  /* n of them, or one for every row (timestep_stride = 0)          */
+  int64_t timestep_stride;   /* 1 or 0                                                          */
+  const void* w1;            /* [d, in_channels]                                                */
+  const void* b1;            /* [d]                                                             */
+  const void* w2;            /* [d, d]                                                          */
+  const void* b2;            /* [d]                                                             */
+  float* workspace;          /* n * d f32                                                       */
+  void* emb;                 /* [n, d]                                                          */
+  int32_t n, in_channels, d;
+  int32_t dtype;
+} p2p_time_embed_args;
+
+int p2p_time_embed(const p2p_time_embed_args* a, p2p_stream_t stream);
+
+/* p2p_time_proj: out_r[n, C_r] = W_r[C_r, d] . silu(emb[n, :]) + b_r for r < segments, in one launch:
+ * the 22 time_emb_proj(F.silu(emb)) of the resnets.  `table` is device memory, 4 int64 per segment:
+ * {W_r, b_r (addresses), s_r, C_r}: out_r starts n * s_r elements into `out` (s_r = the widths in
+ * front of it for packed outputs), so one table serves every n; the weights are read where they
+ * are.  W_r is 16-byte aligned and dense, as is every out_r ([n, C_r]): the caller answers for
+ * the table's contents, which the host cannot see.  tiles = sum over r of ceil(C_r /
+ * P2P_TIME_PROJ_TILE), the launch's workgroups (a larger count is harmless, a smaller one leaves
+ * the last channels unwritten).  Rejected before the launch: a null pointer, n outside
+ * [1, P2P_MAX_BATCH], d outside [1, 2048], segments < 1, tiles < 1 (P2P_E_ARG); d % 8, emb off 16
+ * bytes, table off 8, out off 2 (P2P_E_ALIGN). */
+#define P2P_TIME_PROJ_TILE 16
+typedef struct {
+  const void* emb;           /* [n, d]                                                          */
+  const int64_t* table;      /* [segments, 4], device                                           */
+  void* out;                 /* the arena the table's offsets count from                        */
+  int32_t n, d, segments, tiles;
+  int32_t dtype;
+} p2p_time_proj_args;
+
+int p2p_time_proj(const p2p_time_proj_args* a, p2p_stream_t stream);
+
 /* The image ends of the pipeline (additive to ABI 16; p2p_amd/ptp_utils.py latent2image /
  * image2latent).  Three channels.  dtype: P2P_DTYPE_F32 / BF16 / F16, anything else is
  * P2P_E_DTYPE.  Both take height * width % 4 == 0 only (four pixels per thread, no scalar tail)

@@ -466,6 +466,16 @@ int p2p_nchw_to_tokens(const p2p_nchw_to_tokens_args* a, p2p_stream_t stream) {
   return run_nchw_to_tokens(*a, (hipStream_t)stream);
 }
 
+int p2p_time_embed(const p2p_time_embed_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_time_embed(*a, (hipStream_t)stream);
+}
+
+int p2p_time_proj(const p2p_time_proj_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_time_proj(*a, (hipStream_t)stream);
+}
+
 int p2p_image_u8(const p2p_image_u8_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
   return run_image_u8(*a, (hipStream_t)stream);

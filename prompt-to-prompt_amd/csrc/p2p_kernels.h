@@ -197,6 +197,9 @@ constexpr int64_t gn_bwd_workspace_floats(int64_t n, int64_t channels, int64_t h
 int run_group_norm_bwd(const p2p_group_norm_bwd_args& a, hipStream_t st);
 int run_geglu_bwd(const p2p_geglu_bwd_args& a, hipStream_t st);
 int run_nchw_to_tokens(const p2p_nchw_to_tokens_args& a, hipStream_t st);
+// the time path (p2p_unet.hip): every argument check happens in these, before the launch
+int run_time_embed(const p2p_time_embed_args& a, hipStream_t st);
+int run_time_proj(const p2p_time_proj_args& a, hipStream_t st);
 // the image ends (p2p_image.hip): every argument check happens in these, before the launch
 int run_image_u8(const p2p_image_u8_args& a, hipStream_t st);
 int run_image_to_model(const p2p_image_to_model_args& a, hipStream_t st);

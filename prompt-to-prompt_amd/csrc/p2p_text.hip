@@ -258,6 +258,107 @@ __global__ __launch_bounds__(64 * kLnRowsPerBlock) void layer_norm_kernel(p2p_la
   }
 }
 
+// The many-row form, for the U-Net's transformer blocks (thousands of rows of 320 or 640 channels):
+// LPR lanes per row, 64 / LPR rows per wave, so that no lane idles at C = 40 LPR and a wave has
+// 64 / LPR times the bytes in flight.  Lane l of a row's group holds vectors l, l + LPR, ..; the
+// sums run over the lane's vectors in that order, then over the group by xor-shuffles: a fixed
+// order, but not layer_norm_kernel's, so the host gives this form only the plain norms (no add) of
+// channels <= kLnGroupedMaxChannels, below the text encoders' widths: where it measured faster.
+constexpr int kLnGroupVecs = 5;
+constexpr int kLnGroupedMaxChannels = 16 * kLnGroupVecs * 8;   // 640
+constexpr int kLnGroupedThreads = 256;
+
+template <int LPR>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int o = LPR / 2; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+template <bool F16, int LPR>
+__global__ __launch_bounds__(kLnGroupedThreads) void layer_norm_grouped_kernel(p2p_layer_norm_args a) {
+  constexpr int kRows = kLnGroupedThreads / LPR;   // rows per workgroup
+  const int sub = threadIdx.x % LPR;
+  const int64_t row = (int64_t)blockIdx.x * kRows + threadIdx.x / LPR;
+  // a group past the last row loads and stores nothing, but stays for the shuffles of its wave
+  const bool live = row < a.rows;
+  const int nv = a.channels >> 3;
+  const int64_t base = live ? row * a.channels : 0;
+  const uint16_t* const x = static_cast<const uint16_t*>(a.x) + base;
+  const uint16_t* const add = a.add ? static_cast<const uint16_t*>(a.add) + base : nullptr;
+  const uint16_t* const bias = static_cast<const uint16_t*>(a.add_bias);
+  uint16_t* const sum_out = a.sum_out ? static_cast<uint16_t*>(a.sum_out) + base : nullptr;
+  u16x8_t vx[kLnGroupVecs], va[kLnGroupVecs];
+  // every load of the row first
+#pragma unroll
+  for (int i = 0; i < kLnGroupVecs; ++i) {
+    const int iv = sub + LPR * i;
+    vx[i] = u16x8_t{};
+    va[i] = u16x8_t{};
+    if (live && iv < nv) {
+      vx[i] = *reinterpret_cast<const u16x8_t*>(x + 8 * iv);
+      if (add) va[i] = *reinterpret_cast<const u16x8_t*>(add + 8 * iv);
+    }
+  }
+  float s[kLnGroupVecs][8];
+  float tot = 0.f;
+#pragma unroll
+  for (int i = 0; i < kLnGroupVecs; ++i) {
+    const int iv = sub + LPR * i;
+    if (live && iv < nv) {
+      u16x8_t vb = {}, vs;
+      if (bias) vb = *reinterpret_cast<const u16x8_t*>(bias + 8 * iv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float t = ld16<F16>(vx[i][j]);
+        if (add) t += ld16<F16>(va[i][j]);
+        if (bias) t += ld16<F16>(vb[j]);
+        vs[j] = st16<F16>(t);
+        // the statistics and y come from the rounded sum, as in layer_norm_kernel
+        s[i][j] = ld16<F16>(vs[j]);
+        tot += s[i][j];
+      }
+      if (sum_out) *reinterpret_cast<u16x8_t*>(sum_out + 8 * iv) = vs;
+    }
+  }
+  const float inv_c = 1.f / (float)a.channels;
+  const float mean = group_sum<LPR>(tot) * inv_c;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < kLnGroupVecs; ++i)
+    if (live && sub + LPR * i < nv) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = s[i][j] - mean;
+        q += d * d;
+      }
+    }
+  const float rstd = 1.f / sqrtf(group_sum<LPR>(q) * inv_c + a.eps);
+  const uint16_t* const gamma = static_cast<const uint16_t*>(a.gamma);
+  const uint16_t* const beta = static_cast<const uint16_t*>(a.beta);
+  uint16_t* const y = static_cast<uint16_t*>(a.y) + base;
+#pragma unroll
+  for (int i = 0; i < kLnGroupVecs; ++i) {
+    const int iv = sub + LPR * i;
+    if (live && iv < nv) {
+      const u16x8_t vg = *reinterpret_cast<const u16x8_t*>(gamma + 8 * iv);
+      const u16x8_t vb = *reinterpret_cast<const u16x8_t*>(beta + 8 * iv);
+      u16x8_t o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        o[j] = st16<F16>((s[i][j] - mean) * rstd * ld16<F16>(vg[j]) + ld16<F16>(vb[j]));
+      *reinterpret_cast<u16x8_t*>(y + 8 * iv) = o;
+    }
+  }
+}
+
+template <bool F16, int LPR>
+void launch_layer_norm_grouped(const p2p_layer_norm_args& a, hipStream_t st) {
+  constexpr int kRows = kLnGroupedThreads / LPR;
+  const dim3 grid((unsigned)((a.rows + kRows - 1) / kRows)), block(kLnGroupedThreads);
+  launch_kernel((layer_norm_grouped_kernel<F16, LPR>), grid, block, 0, st, a);
+}
+
 // out[m, j] = act(h), h = in[m, j] + bias[j]; act: h * sigmoid(1.702 h), or (ERF) the exact GELU
 // 0.5 h (1 + erf(h / sqrt 2)) as geglu_kernel (p2p_unet.hip) writes it
 template <bool F16, bool ERF>
@@ -304,9 +405,24 @@ int run_layer_norm(const p2p_layer_norm_args& a, hipStream_t st) {
   if (!aligned16(a.x) || !aligned16(a.add) || !aligned16(a.add_bias) || !aligned16(a.gamma) || !aligned16(a.beta) ||
       !aligned16(a.sum_out) || !aligned16(a.y))
     return P2P_E_ALIGN;
-  const dim3 grid((unsigned)((a.rows + kLnRowsPerBlock - 1) / kLnRowsPerBlock)), block(64 * kLnRowsPerBlock);
-  if (a.dtype == P2P_DTYPE_F16) launch_kernel(layer_norm_kernel<true>, grid, block, 0, st, a);
-  else launch_kernel(layer_norm_kernel<false>, grid, block, 0, st, a);
+  const bool f16 = a.dtype == P2P_DTYPE_F16;
+  // the row mapping is a function of the width and of whether there is an `add` (so are a row's
+  // bits): the plain norm takes 8 lanes per row up to 320 channels and 16 up to 640 -- measured 11 %
+  // and 3 % faster there than a wave per row; with an add a wave already has two operands in flight
+  // and the grouped form measured 1.5-5 % slower, so every add, and every width above 640 (all the
+  // text encoders'), keeps a wave per row
+  const bool grouped = !a.add && a.channels <= kLnGroupedMaxChannels;
+  if (grouped && a.channels <= kLnGroupedMaxChannels / 2) {
+    if (f16) launch_layer_norm_grouped<true, 8>(a, st);
+    else launch_layer_norm_grouped<false, 8>(a, st);
+  } else if (grouped) {
+    if (f16) launch_layer_norm_grouped<true, 16>(a, st);
+    else launch_layer_norm_grouped<false, 16>(a, st);
+  } else {
+    const dim3 grid((unsigned)((a.rows + kLnRowsPerBlock - 1) / kLnRowsPerBlock)), block(64 * kLnRowsPerBlock);
+    if (f16) launch_kernel(layer_norm_kernel<true>, grid, block, 0, st, a);
+    else launch_kernel(layer_norm_kernel<false>, grid, block, 0, st, a);
+  }
   return (int)hipGetLastError();
 }
 

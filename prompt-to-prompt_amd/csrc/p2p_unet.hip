@@ -588,6 +588,140 @@ __global__ __launch_bounds__(256) void nchw_to_tokens_kernel(p2p_nchw_to_tokens_
   }
 }
 
+// ---- the time path: out[n, c] = W[c, :] . act(in[n, :]) + b[c] for N <= 64 rows, a skinny GEMM
+// whose traffic is W.  One wave per kTimeChannelsPerWave rows of W, held in registers (16-bit, as
+// loaded: every load of the workgroup is issued before anything else); the activated input rows,
+// f32, in LDS, kTimeRows at a time, so W is read once whatever N is.  A dot product is the lane's
+// own vectors in order, then the xor tree over the wave: a fixed order.  Three inputs:
+//   kTimeSinusoid  in[n, :] = [cos(t_n f_i), sin(t_n f_i)], f_i = exp(-ln(10000) i / half), from the
+//                  int64 timesteps (accurate cosf / sinf / expf: the arguments reach 999 rad)
+//   kTimeF32Silu   silu of an f32 row (linear_1's unrounded output)
+//   kTimeIoSilu    silu of a 16-bit row (emb)
+// and the output in f32 (linear_1) or rounded once to the tensor type.
+enum { kTimeSinusoid = 0, kTimeF32Silu = 1, kTimeIoSilu = 2 };
+constexpr int kTimeVecs = 4;                                  // rows of W of up to 64 * 4 * 8 = 2048 elements
+constexpr int kTimeMaxD = 64 * kTimeVecs * 8;
+constexpr int kTimeChannelsPerWave = 4;
+constexpr int kTimeWaves = 4;
+constexpr int kTimeTile = kTimeChannelsPerWave * kTimeWaves;  // output channels per workgroup
+constexpr int kTimeRows = 8;                                  // input rows in LDS at a time
+static_assert(kTimeTile == P2P_TIME_PROJ_TILE, "p2p_time_proj_args.tiles counts tiles of this many channels");
+
+struct TimeLinearArgs {
+  const void* in;            // f32 or 16-bit [n, d]; unused for kTimeSinusoid
+  const int64_t* timesteps;  // kTimeSinusoid: n timesteps, timestep_stride apart (0: one for all rows)
+  int64_t timestep_stride;
+  const void* w;             // one segment: [channels, d], bias [channels], out [n, channels] ...
+  const void* b;
+  void* out;
+  int channels;
+  const int64_t* table;      // ... or `segments` rows of {W, b, s_r, C_r}: out_r starts n * s_r elements into `out`
+  int segments;
+  int n, d;
+};
+
+template <bool F16, int IN>
+__global__ __launch_bounds__(64 * kTimeWaves) void time_linear_kernel(TimeLinearArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float act[];   // [kTimeRows][d]
+  constexpr bool OUT_F32 = IN == kTimeSinusoid;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  // this workgroup's segment and its first channel there (workgroup-uniform)
+  const uint16_t* w = static_cast<const uint16_t*>(a.w);
+  const uint16_t* b = static_cast<const uint16_t*>(a.b);
+  int64_t out_off = 0;
+  int C = a.channels;
+  int c0 = blockIdx.x * kTimeTile;
+  if (a.table) {
+    int tile = blockIdx.x, r = 0;
+    for (; r < a.segments; ++r) {
+      const int tiles = ((int)a.table[4 * r + 3] + kTimeTile - 1) / kTimeTile;
+      if (tile < tiles) break;
+      tile -= tiles;
+    }
+    if (r == a.segments) return;   // a grid larger than the table's tiles
+    w = reinterpret_cast<const uint16_t*>(a.table[4 * r]);
+    b = reinterpret_cast<const uint16_t*>(a.table[4 * r + 1]);
+    out_off = a.table[4 * r + 2] * a.n;
+    C = (int)a.table[4 * r + 3];
+    c0 = tile * kTimeTile;
+  }
+  const int D = a.d, nv = D >> 3;
+  const int cw = c0 + wave * kTimeChannelsPerWave;   // this wave's first channel
+  u16x8_t wv[kTimeChannelsPerWave][kTimeVecs];
+#pragma unroll
+  for (int k = 0; k < kTimeChannelsPerWave; ++k)
+#pragma unroll
+    for (int i = 0; i < kTimeVecs; ++i) {
+      const int iv = lane + 64 * i;
+      wv[k][i] = u16x8_t{};
+      if (cw + k < C && iv < nv) wv[k][i] = *reinterpret_cast<const u16x8_t*>(w + (int64_t)(cw + k) * D + 8 * iv);
+    }
+  float bias[kTimeChannelsPerWave];
+#pragma unroll
+  for (int k = 0; k < kTimeChannelsPerWave; ++k) bias[k] = cw + k < C ? ld16<F16>(b[cw + k]) : 0.f;
+
+  for (int n0 = 0; n0 < a.n; n0 += kTimeRows) {
+    const int rows = min(kTimeRows, a.n - n0);
+    __syncthreads();   // the previous rows have been read
+    for (int e = threadIdx.x; e < rows * D; e += 64 * kTimeWaves) {
+      // (row, column) of element e; rows <= 8, so the row is found by counting, not by a division
+      int n = 0;
+      while ((n + 1) * D <= e) ++n;
+      const int j = e - n * D;
+      float v;
+      if (IN == kTimeSinusoid) {
+        const int half = D >> 1;
+        const int i = j < half ? j : j - half;
+        const float f = expf(-9.210340371976184f * (float)i / (float)half);
+        const float arg = (float)a.timesteps[(n0 + n) * a.timestep_stride] * f;
+        v = j < half ? cosf(arg) : sinf(arg);
+      } else if (IN == kTimeF32Silu) {
+        const float h = static_cast<const float*>(a.in)[(int64_t)(n0 + n) * D + j];
+        v = h / (1.f + expf(-h));
+      } else {
+        const float h = ld16<F16>(static_cast<const uint16_t*>(a.in)[(int64_t)(n0 + n) * D + j]);
+        v = h / (1.f + expf(-h));
+      }
+      act[n * D + j] = v;
+    }
+    __syncthreads();
+    for (int n = 0; n < rows; ++n) {
+      float acc[kTimeChannelsPerWave] = {};
+#pragma unroll
+      for (int i = 0; i < kTimeVecs; ++i) {
+        const int iv = lane + 64 * i;
+        if (iv < nv) {
+          const float4 lo = *reinterpret_cast<const float4*>(act + n * D + 8 * iv);
+          const float4 hi = *reinterpret_cast<const float4*>(act + n * D + 8 * iv + 4);
+          const float av[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+          for (int k = 0; k < kTimeChannelsPerWave; ++k)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[k] += ld16<F16>(wv[k][i][j]) * av[j];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kTimeChannelsPerWave; ++k) {
+        for (int o = 32; o; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+        // lane k stores channel cw + k of row n0 + n
+        if (lane == k && cw + k < C) {
+          const float y = acc[k] + bias[k];
+          const int64_t at = out_off + (int64_t)(n0 + n) * C + cw + k;
+          if (OUT_F32) static_cast<float*>(a.out)[at] = y;
+          else static_cast<uint16_t*>(a.out)[at] = st16<F16>(y);
+        }
+      }
+    }
+  }
+}
+
+template <bool F16, int IN>
+void launch_time_linear(const TimeLinearArgs& a, int tiles, hipStream_t st) {
+  const uint32_t lds = (uint32_t)(min(a.n, kTimeRows) * a.d * sizeof(float));   // <= 64 KB
+  launch_kernel((time_linear_kernel<F16, IN>), dim3((unsigned)tiles), dim3(64 * kTimeWaves), lds, st, a);
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool io16(int dtype) { return dtype == P2P_DTYPE_BF16 || dtype == P2P_DTYPE_F16; }
 
@@ -735,6 +869,47 @@ int run_bias_residual(const p2p_bias_residual_args& a, hipStream_t st) {
   if (!aligned16(a.a) || !aligned16(a.b) || !aligned16(a.out)) return P2P_E_ALIGN;
   if (a.dtype == P2P_DTYPE_F16) launch_bias_residual<true>(a, st);
   else launch_bias_residual<false>(a, st);
+  return (int)hipGetLastError();
+}
+
+int run_time_embed(const p2p_time_embed_args& a, hipStream_t st) {
+  if (!a.timesteps || !a.w1 || !a.b1 || !a.w2 || !a.b2 || !a.workspace || !a.emb) return P2P_E_ARG;
+  if (a.n < 1 || a.n > P2P_MAX_BATCH || a.in_channels < 1 || a.d < 1) return P2P_E_ARG;
+  if (a.in_channels > kTimeMaxD || a.d > kTimeMaxD) return P2P_E_ARG;
+  if (a.timestep_stride != 0 && a.timestep_stride != 1) return P2P_E_ARG;
+  if (!io16(a.dtype)) return P2P_E_DTYPE;
+  if (a.in_channels % 8 || a.d % 8) return P2P_E_ALIGN;
+  if (!aligned16(a.w1) || !aligned16(a.w2) || !aligned16(a.workspace) || !aligned16(a.emb)) return P2P_E_ALIGN;
+  if (((uintptr_t)a.timesteps & 7) || ((uintptr_t)a.b1 & 1) || ((uintptr_t)a.b2 & 1)) return P2P_E_ALIGN;
+  const int tiles = (a.d + kTimeTile - 1) / kTimeTile;
+  const bool f16 = a.dtype == P2P_DTYPE_F16;
+  TimeLinearArgs l1 = {};
+  l1.timesteps = a.timesteps; l1.timestep_stride = a.timestep_stride;
+  l1.w = a.w1; l1.b = a.b1; l1.out = a.workspace; l1.channels = a.d;
+  l1.n = a.n; l1.d = a.in_channels;
+  if (f16) launch_time_linear<true, kTimeSinusoid>(l1, tiles, st);
+  else launch_time_linear<false, kTimeSinusoid>(l1, tiles, st);
+  TimeLinearArgs l2 = {};
+  l2.in = a.workspace;
+  l2.w = a.w2; l2.b = a.b2; l2.out = a.emb; l2.channels = a.d;
+  l2.n = a.n; l2.d = a.d;
+  if (f16) launch_time_linear<true, kTimeF32Silu>(l2, tiles, st);
+  else launch_time_linear<false, kTimeF32Silu>(l2, tiles, st);
+  return (int)hipGetLastError();
+}
+
+int run_time_proj(const p2p_time_proj_args& a, hipStream_t st) {
+  if (!a.emb || !a.table || !a.out) return P2P_E_ARG;
+  if (a.n < 1 || a.n > P2P_MAX_BATCH || a.d < 1 || a.d > kTimeMaxD || a.segments < 1 || a.tiles < 1) return P2P_E_ARG;
+  if (!io16(a.dtype)) return P2P_E_DTYPE;
+  if (a.d % 8) return P2P_E_ALIGN;
+  if (!aligned16(a.emb) || ((uintptr_t)a.table & 7) || ((uintptr_t)a.out & 1)) return P2P_E_ALIGN;
+  TimeLinearArgs l = {};
+  l.in = a.emb; l.out = a.out;
+  l.table = a.table; l.segments = a.segments;
+  l.n = a.n; l.d = a.d;
+  if (a.dtype == P2P_DTYPE_F16) launch_time_linear<true, kTimeIoSilu>(l, a.tiles, st);
+  else launch_time_linear<false, kTimeIoSilu>(l, a.tiles, st);
   return (int)hipGetLastError();
 }
 

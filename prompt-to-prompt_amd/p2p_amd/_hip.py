@@ -158,6 +158,22 @@ class NchwToTokensArgs(ctypes.Structure):
     ]
 
 
+class TimeEmbedArgs(ctypes.Structure):
+    _fields_ = [
+        ("timesteps", ctypes.c_void_p), ("timestep_stride", ctypes.c_int64), ("w1", ctypes.c_void_p),
+        ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("emb", ctypes.c_void_p), ("n", ctypes.c_int32), ("in_channels", ctypes.c_int32), ("d", ctypes.c_int32),
+        ("dtype", ctypes.c_int32),
+    ]
+
+
+class TimeProjArgs(ctypes.Structure):
+    _fields_ = [
+        ("emb", ctypes.c_void_p), ("table", ctypes.c_void_p), ("out", ctypes.c_void_p), ("n", ctypes.c_int32),
+        ("d", ctypes.c_int32), ("segments", ctypes.c_int32), ("tiles", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
 class LayerNormArgs(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("add", ctypes.c_void_p), ("add_bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
@@ -272,6 +288,8 @@ def lib():
         L.p2p_group_norm_bwd_workspace_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_geglu_bwd.argtypes = [ctypes.POINTER(GegluBwdArgs), vp]
         L.p2p_nchw_to_tokens.argtypes = [ctypes.POINTER(NchwToTokensArgs), vp]
+        L.p2p_time_embed.argtypes = [ctypes.POINTER(TimeEmbedArgs), vp]
+        L.p2p_time_proj.argtypes = [ctypes.POINTER(TimeProjArgs), vp]
         L.p2p_causal_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp]
         L.p2p_layer_norm.argtypes = [ctypes.POINTER(LayerNormArgs), vp]
         L.p2p_bias_quick_gelu.argtypes = [ctypes.POINTER(BiasActArgs), vp]
@@ -314,7 +332,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_image_to_model", "p2p_group_norm_stats_floats", "p2p_causal_attn_fwd", "p2p_layer_norm",
                     "p2p_bias_quick_gelu", "p2p_text_attn_fwd", "p2p_bias_gelu", "p2p_maps_aggregate",
                     "p2p_map_panels", "p2p_null_loss", "p2p_null_adam", "p2p_group_norm_bwd",
-                    "p2p_group_norm_bwd_workspace_floats", "p2p_geglu_bwd", "p2p_nchw_to_tokens")
+                    "p2p_group_norm_bwd_workspace_floats", "p2p_geglu_bwd", "p2p_nchw_to_tokens", "p2p_time_embed",
+                    "p2p_time_proj")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -938,6 +957,102 @@ def nchw_to_tokens(src):
     t.dtype = _glue_dtype(src)
     _check(lib().p2p_nchw_to_tokens(ctypes.byref(t), _stream(src.device)), "p2p_nchw_to_tokens")
     return dst
+
+
+# -- the U-Net's time path (p2p_unet.hip).  As the glue above: None where the kernels do not serve
+# the operands (f32, CPU, a width that is no multiple of 8 or above TIME_MAX_D, more than MAX_BATCH rows).
+TIME_MAX_D = 2048
+TIME_PROJ_TILE = 16
+
+
+def _time_operands(ts, d_in: int, n: int) -> bool:
+    first = ts[0]
+    return (all(t.is_cuda and t.dtype == first.dtype and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts)
+            and first.dtype in (torch.bfloat16, torch.float16) and d_in % 8 == 0 and d_in <= TIME_MAX_D
+            and 1 <= n <= MAX_BATCH)
+
+
+def time_embed(timesteps, w1, b1, w2, b2):
+    """linear_2(silu(linear_1([cos(t f_i), sin(t f_i)]))) in the weights' dtype, [N, D], for N int64
+    timesteps on the GPU (p2p_time_embed): timestep_embedding and TimestepEmbedding with f32 between
+    the layers and one rounding at the end.  A stride-0 ``timesteps`` (one step expanded to N rows) is
+    read as it is."""
+    D, d_in = w1.shape
+    N = timesteps.shape[0]
+    if timesteps.dim() != 1 or timesteps.dtype != torch.int64 or not timesteps.is_cuda or \
+            timesteps.stride(0) not in (0, 1) or not _time_operands((w1, b1, w2, b2), d_in, N) or \
+            D % 8 or D > TIME_MAX_D:
+        return None
+    if tuple(w2.shape) != (D, D) or b1.numel() != D or b2.numel() != D:
+        raise HipError(f"time_embed: linear_2 {tuple(w2.shape)} does not follow linear_1 {tuple(w1.shape)}")
+    a = TimeEmbedArgs()
+    a.timesteps, a.timestep_stride = timesteps.data_ptr(), timesteps.stride(0) if N > 1 else 1
+    a.w1, a.b1, a.w2, a.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
+    ws = torch.empty((N, D), dtype=torch.float32, device=w1.device)
+    emb = torch.empty((N, D), dtype=w1.dtype, device=w1.device)
+    a.workspace, a.emb = ws.data_ptr(), emb.data_ptr()
+    a.n, a.in_channels, a.d = N, d_in, D
+    a.dtype = _glue_dtype(w1)
+    return emb if _glue_rc(lib().p2p_time_embed(ctypes.byref(a), _stream(w1.device)), "p2p_time_embed") else None
+
+
+class TimeProjTable:
+    """The device-side segment table of p2p_time_proj for a list of (weight [C_r, D], bias [C_r])
+    pairs, and what it was built from.  Building it copies 4 int64 per segment from pinned memory
+    without waiting for the copy; the pinned allocation itself may synchronise the device, which is
+    why a table is built in an eager call only (once per model and per move of its weights), never
+    under graph capture.  ``valid_for`` compares addresses on the host only."""
+
+    def __init__(self, pairs, gaps: Sequence[int] = ()):
+        """``gaps``: elements (per row of emb) left unwritten in front of each segment's output (the
+        tests poison them); the product packs the segments."""
+        w0 = pairs[0][0]
+        self.d, self.dtype, self.device = w0.shape[1], w0.dtype, w0.device
+        flat = [t for pair in pairs for t in pair]
+        self.supported = all(w.dim() == 2 and w.shape[1] == self.d and b.shape == (w.shape[0],) for w, b in pairs) \
+            and _time_operands(flat, self.d, 1)
+        self.key = self.key_of(pairs)
+        self.widths = [w.shape[0] for w, _ in pairs]
+        gaps = list(gaps) or [0] * len(pairs)
+        self.starts, at = [], 0           # of out_r, in elements per row of emb
+        for c, gap in zip(self.widths, gaps):
+            self.starts.append(at + gap)
+            at += gap + c
+        self.row_elems = at
+        self.tiles = sum((c + TIME_PROJ_TILE - 1) // TIME_PROJ_TILE for c in self.widths)
+        self.table = self._rows = None
+        if self.supported:
+            rows = [[w, b, s, c] for w, b, s, c in zip(self.key[0::2], self.key[1::2], self.starts, self.widths)]
+            self._rows = torch.tensor(rows, dtype=torch.int64).pin_memory()   # alive until the copy has run
+            self.table = self._rows.to(self.device, non_blocking=True)        # [segments, 4]
+
+    @staticmethod
+    def key_of(pairs):
+        return tuple(t.data_ptr() for pair in pairs for t in pair)
+
+    def valid_for(self, pairs) -> bool:
+        return self.key == self.key_of(pairs)
+
+
+def time_proj(emb, table: TimeProjTable, out=None):
+    """[W_r . silu(emb) + b_r for r] as dense [N, C_r] views of one arena (p2p_time_proj): every
+    time_emb_proj(F.silu(emb)) of the U-Net in one launch.  ``out``: None, or a 1-D arena of at least
+    N * table.row_elems elements."""
+    N = emb.shape[0]
+    if not table.supported or emb.dim() != 2 or emb.shape[1] != table.d or emb.dtype != table.dtype or \
+            emb.device != table.device or not emb.is_contiguous() or not 1 <= N <= MAX_BATCH:
+        return None
+    if out is None:
+        out = torch.empty(N * table.row_elems, dtype=emb.dtype, device=emb.device)
+    elif out.dim() != 1 or out.numel() < N * table.row_elems or out.dtype != emb.dtype or not out.is_contiguous():
+        raise HipError("time_proj: out must be a dense 1-D arena of N * row_elems elements")
+    a = TimeProjArgs()
+    a.emb, a.table, a.out = emb.data_ptr(), table.table.data_ptr(), out.data_ptr()
+    a.n, a.d, a.segments, a.tiles = N, table.d, len(table.widths), table.tiles
+    a.dtype = _glue_dtype(emb)
+    if not _glue_rc(lib().p2p_time_proj(ctypes.byref(a), _stream(emb.device)), "p2p_time_proj"):
+        return None
+    return [out[s * N:(s + c) * N].view(N, c) for s, c in zip(table.starts, table.widths)]
 
 
 # -- the image ends (p2p_image.hip).  As the glue above: None where the library reports the shape

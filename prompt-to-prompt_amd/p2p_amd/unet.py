@@ -146,7 +146,34 @@ class BasicTransformerBlock(nn.Module):
         self.norm2 = nn.LayerNorm(dim)
         self.norm3 = nn.LayerNorm(dim)
 
+    def _forward_fused(self, x, context):
+        """Each residual add runs inside the LayerNorm that reads it (p2p_layer_norm: the rounded
+        sum is stored by the launch that normalises it); the attention modules are called as in the
+        torch lines.  The last add has no norm behind it and stays torch's.  Under autograd the same
+        forward runs (unet_grad.layer_norm), so both modes give the same bits."""
+        n1, n2, n3 = self.norm1, self.norm2, self.norm3
+        out = unet_grad.layer_norm(x, n1.weight, n1.bias, n1.eps)
+        if out is None:
+            return None
+        a = self.attn1(out[0])
+        out = unet_grad.layer_norm(x, n2.weight, n2.bias, n2.eps, add=a)
+        if out is None:
+            raise _hip.HipError("p2p_layer_norm took norm1 and refused norm2 of the same block")
+        h, s = out                        # s: the residual stream from here on (x is the caller's)
+        c = self.attn2(h, context=context)
+        out = unet_grad.layer_norm(s, n3.weight, n3.bias, n3.eps, add=c)
+        if out is None:
+            raise _hip.HipError("p2p_layer_norm took norm1 and refused norm3 of the same block")
+        h, s = out
+        return self.ff(h) + s
+
     def forward(self, x, context=None):
+        norms = (self.norm1, self.norm2, self.norm3)
+        if fused_glue(x, self.norm1.weight) or fused_glue_grad(
+                x, params=[p for n in norms for p in (n.weight, n.bias)]):
+            out = self._forward_fused(x, context)
+            if out is not None:
+                return out
         x = self.attn1(self.norm1(x)) + x
         x = self.attn2(self.norm2(x), context=context) + x
         return self.ff(self.norm3(x)) + x
@@ -205,15 +232,19 @@ class ResnetBlock2D(nn.Module):
         self.conv2 = nn.Conv2d(out_ch, out_ch, 3, padding=1)
         self.conv_shortcut = nn.Conv2d(in_ch, out_ch, 1) if in_ch != out_ch else None
 
-    def _forward_fused(self, x, temb):
+    def _forward_fused(self, x, temb, proj=None):
         """Both norms with their SiLU in one launch each; the convs run without bias: conv1's and
-        the time embedding are added on load by norm2, conv2's and the shortcut's by the residual."""
+        the time embedding are added on load by norm2, conv2's and the shortcut's by the residual.
+        ``proj``: this block's time_emb_proj(F.silu(temb)) where the U-Net has computed it already."""
         c1, c2, sc = self.conv1, self.conv2, self.conv_shortcut
         h = _norm_act(self.norm1, x, silu=True)
         if h is None:
             return None
         h = c1._conv_forward(h, c1.weight, None)
-        chan_add = self.time_emb_proj(F.silu(temb)) if temb is not None else None
+        if proj is not None:
+            chan_add = proj
+        else:
+            chan_add = self.time_emb_proj(F.silu(temb)) if temb is not None else None
         h = _norm_act(self.norm2, h, silu=True, chan_add=chan_add, chan_bias=c1.bias)
         if h is None:
             return None
@@ -228,9 +259,12 @@ class ResnetBlock2D(nn.Module):
         return (*self.parameters(), temb)
 
     def forward(self, x, temb=None):
+        proj = None
+        if isinstance(temb, TimeProjections):     # from UNet2DConditionModel.forward, fused inference only
+            temb, proj = temb.emb, temb.of(self)
         if fused_glue(x, self.conv1.weight, *(() if temb is None else (temb,))) or fused_glue_grad(
                 x, params=self._glue_params(temb), norms=(self.norm1, self.norm2)):
-            out = self._forward_fused(x, temb)
+            out = self._forward_fused(x, temb, proj)
             if out is not None:
                 return out
         h = self.conv1(F.silu(self.norm1(x)))
@@ -360,6 +394,25 @@ def timestep_embedding(timesteps: torch.Tensor, dim: int, max_period: int = 1000
     return torch.cat([torch.cos(emb), torch.sin(emb)], dim=-1)
 
 
+# The fused time path is adopted up to this many rows: measured at N = 8 it takes 96 us against the
+# torch lines' 222 us, at N = 64 (--groups-per-call 8) 642 us against 235 us -- the kernels stage the
+# activations once per workgroup and 8-row chunk -- so larger batches keep the torch lines
+# (profiles/r15/transformer_glue/unet_ln_bench.txt)
+TIME_FUSED_MAX_ROWS = 8
+
+
+class TimeProjections:
+    """What UNet2DConditionModel.forward hands its blocks in place of ``emb`` when the time path has
+    run on the HIP kernels: ``emb`` itself and, per resnet, its time_emb_proj(F.silu(emb)) -- dense
+    [N, C] views of one arena, computed up front in one launch."""
+
+    def __init__(self, emb, by_linear):
+        self.emb, self._by_linear = emb, by_linear
+
+    def of(self, resnet):
+        return self._by_linear.get(getattr(resnet, "time_emb_proj", None))
+
+
 class TimestepEmbedding(nn.Module):
     def __init__(self, in_ch, dim):
         super().__init__()
@@ -405,10 +458,40 @@ class UNet2DConditionModel(nn.Module):
                                                          cross_attention_dim, upsample=not last, temb_ch=temb))
         self.conv_norm_out = nn.GroupNorm(32, boc[0], eps=1e-5)
         self.conv_out = nn.Conv2d(boc[0], out_channels, 3, padding=1)
+        # the resnets' time projections, in module order: the segments of p2p_time_proj (a plain
+        # tuple: the modules are registered where they live)
+        self._time_linears = tuple(m.time_emb_proj for m in self.modules() if isinstance(m, ResnetBlock2D))
+        self._time_proj_table = None
 
     @property
     def dtype(self):
         return self.conv_in.weight.dtype
+
+    def _time_path_fused(self, timestep):
+        """emb and every resnet's time projection in three launches (p2p_time_embed, p2p_time_proj),
+        as a TimeProjections; None -- the torch lines -- where a parameter of the path requires grad
+        or the kernels do not serve the operands.  The segment table of the projections is built
+        once and again whenever a weight has moved (``.to()``; an in-place load_state_dict keeps the
+        addresses): a host-side comparison and, to build, one asynchronous copy from pinned memory,
+        not under graph capture -- a capture whose model has no valid table runs the torch lines."""
+        te = self.time_embedding
+        linears = self._time_linears
+        pairs = [(m.weight, m.bias) for m in linears]
+        params = (*te.parameters(), *(t for pair in pairs for t in pair))
+        if any(p.requires_grad for p in params) or timestep.dtype != torch.int64 or not timestep.is_cuda:
+            return None
+        if timestep.shape[0] > TIME_FUSED_MAX_ROWS:
+            return None
+        table = self._time_proj_table
+        if table is None or not table.valid_for(pairs):
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            table = self._time_proj_table = _hip.TimeProjTable(pairs)
+        emb = _hip.time_embed(timestep, te.linear_1.weight, te.linear_1.bias, te.linear_2.weight, te.linear_2.bias)
+        if emb is None:
+            return None
+        outs = _hip.time_proj(emb, table)
+        return emb if outs is None else TimeProjections(emb, dict(zip(linears, outs)))
 
     def forward(self, sample, timestep, encoder_hidden_states):
         if not torch.is_tensor(timestep):
@@ -416,7 +499,9 @@ class UNet2DConditionModel(nn.Module):
         elif timestep.dim() == 0:
             timestep = timestep[None].to(sample.device)
         timestep = timestep.expand(sample.shape[0])
-        emb = self.time_embedding(timestep_embedding(timestep, self.conv_in.out_channels).to(self.dtype))
+        emb = self._time_path_fused(timestep) if fused_glue(self.time_embedding.linear_1.weight) else None
+        if emb is None:
+            emb = self.time_embedding(timestep_embedding(timestep, self.conv_in.out_channels).to(self.dtype))
         ctx = encoder_hidden_states.to(self.dtype)
         x = self.conv_in(sample.to(self.dtype))
         skips = (x,)

@@ -8,6 +8,10 @@ the host or reads a value back, so a step that goes through these functions capt
 graph.  A call whose tensors do not require grad goes straight to the inference binding and costs
 what it costs there (the layers ahead of the first cross-attention, in null-text inversion).
 
+LayerNorm (the transformer blocks') has no HIP backward: ``_LayerNorm`` runs the p2p_layer_norm
+forward, so that the autograd and no-grad forwards share their bits, and takes torch's gradient of
+F.layer_norm at the saved sum.
+
 The wrappers return None where the forward binding reports the input unsupported, as the bindings
 do; a backward binding that rejects what its forward served raises ``HipError``.
 """
@@ -81,6 +85,37 @@ class _BiasResidual(torch.autograd.Function):
         return da, db, None, None, None
 
 
+class _LayerNorm(torch.autograd.Function):
+    """(LN(x + add), the rounded sum) from p2p_layer_norm: the bits of the no-grad forward.  The
+    library has no LayerNorm backward; the gradient is torch's own, taken through F.layer_norm at the
+    saved sum -- what the torch lines compute from the same 16-bit tensor.  Saves the sum only."""
+
+    @staticmethod
+    def forward(ctx, x, add, gamma, beta, eps):
+        s = torch.empty_like(x) if add is not None else x
+        y = _hip.layer_norm(x, gamma, beta, eps, add=add, sum_out=s if add is not None else None)
+        if y is None:
+            raise _hip.HipError(f"layer_norm under autograd: {tuple(x.shape)} {x.dtype} is not served")
+        ctx.save_for_backward(s, gamma, beta)
+        ctx.eps, ctx.has_add = eps, add is not None
+        if add is None:          # no sum of its own: the caller keeps x
+            s = x.new_empty(0)
+            ctx.mark_non_differentiable(s)
+        return y, s
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy, ds):
+        s, gamma, beta = ctx.saved_tensors
+        with torch.enable_grad():
+            leaf = s.detach().requires_grad_(True)
+            out = torch.nn.functional.layer_norm(leaf, (s.shape[-1],), gamma, beta, ctx.eps)
+            g, = torch.autograd.grad(out, leaf, dy)
+        if ctx.has_add:                  # the sum's own gradient reaches both of its operands
+            g = g + ds
+        return (g if ctx.needs_input_grad[0] else None), (g if ctx.needs_input_grad[1] else None), None, None, None
+
+
 def _dense16(x: torch.Tensor) -> bool:
     return x.dim() == 4 and x.is_contiguous()
 
@@ -104,6 +139,23 @@ def geglu(x):
     if x.shape[-1] % 2 or x2.stride(-1) != 1 or x2.data_ptr() != x.data_ptr():
         return None
     return _Geglu.apply(x)
+
+
+def layer_norm(x, gamma, beta, eps: float, add=None):
+    """(LN(x + add), x + add rounded) on _hip.layer_norm, differentiable with respect to x and add
+    (``add`` None: (LN(x), x)).  None where the binding does not serve the operands."""
+    if add is not None and (add.shape != x.shape or add.dtype != x.dtype or not add.is_contiguous()):
+        return None
+    if not (x.requires_grad or (add is not None and add.requires_grad)):
+        s = torch.empty_like(x) if add is not None else x
+        y = _hip.layer_norm(x, gamma, beta, eps, add=add, sum_out=s if add is not None else None)
+        return None if y is None else (y, s)
+    C = x.shape[-1]
+    if not x.is_cuda or not x.is_contiguous() or x.dtype not in (torch.bfloat16, torch.float16) or C % 8 or \
+            C > _hip.LN_MAX_CHANNELS or gamma.dtype != x.dtype or beta.dtype != x.dtype:
+        return None
+    y, s = _LayerNorm.apply(x, add, gamma, beta, float(eps))
+    return y, (s if add is not None else x)
 
 
 def bias_residual(a_nchw, b, bias=None, bias2=None, tokens: bool = False):

@@ -9,7 +9,10 @@ import sys
 GLUE = ("CUDAFunctor_add", "direct_copy_kernel", "RowwiseMoments", "GroupNormKernelImpl", "ComputeFusedParams",
         "silu_kernel", "GeluCUDAKernelImpl", "BinaryFunctor", "batched_transpose", "SubTensorOp",
         "gn_stats_kernel", "gn_apply_nchw_kernel", "gn_apply_tok_kernel", "bias_residual_nchw_kernel",
-        "bias_residual_tok_kernel", "geglu_kernel")
+        "bias_residual_tok_kernel", "geglu_kernel",
+        # the transformer blocks' LayerNorms and the time path (torch's, then csrc/p2p_text.hip / p2p_unet.hip)
+        "vectorized_layer_norm_kernel", "layer_norm_grouped_kernel", "layer_norm_kernel", "MT16x16x128",
+        "time_linear_kernel")
 
 
 def short(name):

@@ -34,7 +34,8 @@ def main():
     _hip.check_source_hash()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    model = unet.UNet2DConditionModel().to(dev, torch.bfloat16).eval()
+    # (frozen, as the pipelines load it: the fused time path declines parameters that require grad)
+    model = unet.UNet2DConditionModel().to(dev, torch.bfloat16).eval().requires_grad_(False)
     g = torch.Generator(device=dev).manual_seed(1)
     x = torch.randn(8, 4, 64, 64, device=dev, generator=g)
     ctx = torch.randn(8, 77, 768, device=dev, generator=g)
