@@ -215,15 +215,19 @@ int p2p_attn_bwd(const p2p_attn_tensors* t, const void* dout, const float* lse, 
                  p2p_stream_t stream);
 
 /* LocalBlend (null_text.py:41-70; main.py:35-52 is the B=2 special case) for one prompt
- * group: maps[l] are the running-sum cross maps of the five 16x16 layers
- * (down_cross[2:4] + up_cross[:3]), each [n_prompts * heads_per_map, 256, n_words] f32. */
+ * group: maps[l] are the running-sum cross maps of the blended layers (Stable Diffusion: the
+ * five 16x16 layers down_cross[2:4] + up_cross[:3]), each [n_prompts * heads_per_map,
+ * map_res^2, n_words] f32.  Served, and tested at their edges (tests/test_gpu_blend_geometry.py):
+ * 1 <= n_prompts <= 16, 1 <= n_maps <= 8, n_words <= 128, map_res^2 <= 256 (any map_res, odd
+ * ones included), any heads_per_map >= 1 and any lat_h, lat_w >= 1 -- larger or smaller than
+ * map_res, square or not (nearest resampling as F.interpolate's); anything else is P2P_E_ARG. */
 typedef struct {
   const float* maps[8];
   int32_t n_maps;
   int32_t heads_per_map;
   int32_t n_prompts;
   int32_t n_words;
-  int32_t map_res;                 /* 16                                               */
+  int32_t map_res;                 /* maps are map_res x map_res; map_res^2 <= 256     */
   const float* alpha_layers;       /* [n_prompts, n_words]                             */
   const float* substruct_layers;   /* [n_prompts, n_words] or NULL                     */
   float th_pool, th_sub;           /* th[0], th[1] (main form: threshold, unused)      */
@@ -274,8 +278,10 @@ typedef struct {
    * null_text.py:68-70 follows.  `mask` must then be NULL; NULL entries do not blend.
    * (ptp_utils.py:75 step_callback + null_text.py:41-70, fused with the CFG/DDIM update.) */
   const float* blend_sums[P2P_MAX_GROUPS];
-  int32_t blend_lh;                /* layer x head maps per prompt (5 x 8)                   */
-  int32_t blend_res;               /* map resolution (16); res^2 <= 256, <= lat_h, lat_w     */
+  int32_t blend_lh;                /* layer x head maps per prompt, any >= 1 (SD: 5 x 8)     */
+  int32_t blend_res;               /* map resolution >= 1; res^2 <= 256, res <= height, width;
+                                      height * width % 4 == 0; x, out, eps 16-byte aligned;
+                                      any channels >= 1 (else P2P_E_ARG, before any launch)  */
   float blend_th_pool, blend_th_sub;
   int32_t blend_sub;               /* 1: the substruct sums (index 1) gate the mask          */
 } p2p_latent_step_args;

@@ -103,6 +103,60 @@ def test_localblend_rejects():
     assert L.p2p_store_scale(None, None, 1.0, 10, None) == -1
 
 
+def _blend_args(**kw):
+    """p2p_localblend arguments inside every limit (dummy pointers: nothing may be launched)."""
+    a = _hip.BlendArgs()
+    for l in range(5):
+        a.maps[l] = 1 << 20
+    a.n_maps, a.heads_per_map, a.n_prompts, a.n_words, a.map_res = 5, 8, 4, 77, 16
+    a.alpha_layers, a.th_pool, a.th_sub = 1 << 21, 0.3, 0.3
+    a.x_t, a.channels, a.lat_h, a.lat_w = 1 << 22, 4, 64, 64
+    a.word_sums, a.mask_out = 1 << 23, 1 << 24
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+@pytest.mark.parametrize("kw", [dict(n_prompts=17), dict(map_res=17), dict(n_words=129), dict(n_maps=9),
+                                dict(x_t=None, mask_out=None), dict(n_prompts=0), dict(n_maps=0),
+                                dict(alpha_layers=None), dict(word_sums=None), dict(lat_h=0), dict(lat_w=0)],
+                         ids=lambda kw: "-".join(f"{k}={v}" for k, v in kw.items()))
+def test_localblend_rejects_past_its_limits(kw):
+    """The limits include/p2p_hip.h states for p2p_localblend: one past each is P2P_E_ARG."""
+    assert _hip.lib().p2p_localblend(ctypes.byref(_blend_args(**kw)), None) == -1
+
+
+def _step_args(cls, kw):
+    """p2p_latent_step / p2p_plms_step arguments of the one-launch LocalBlend form, inside every
+    limit (dummy pointers)."""
+    a = cls()
+    a.eps, a.x, a.out = 1024, 2048, 4096
+    a.eps_dtype, a.cfg, a.guidance = 0, 1, 7.5
+    a.n_prompts, a.channels, a.height, a.width = 4, 4, 64, 64
+    a.blend_sums[0], a.blend_lh, a.blend_res = 1 << 20, 40, 16
+    a.blend_th_pool, a.blend_th_sub = 0.3, 0.3
+    if cls is _hip.PlmsArgs:
+        a.n_hist, a.w[0], a.sample_coeff, a.eps_num, a.eps_den = 0, 1.0, 1.01, 0.02, 0.5
+    else:
+        a.sqrt_beta_t, a.sqrt_alpha_t, a.sqrt_alpha_prev, a.sqrt_one_minus_alpha_prev = 0.6, 0.8, 0.85, 0.52
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+@pytest.mark.parametrize("entry", ["p2p_latent_step", "p2p_plms_step"])
+@pytest.mark.parametrize("kw", [dict(height=12), dict(width=12), dict(height=17, width=17), dict(blend_res=17),
+                                dict(x=2052), dict(out=4100), dict(eps=1028), dict(mask=512), dict(group_blend=512),
+                                dict(out=2048), dict(blend_lh=0), dict(blend_res=0)],
+                         ids=lambda kw: "-".join(f"{k}={v}" for k, v in kw.items()))
+def test_one_launch_latent_step_rejects(entry, kw):
+    """The one-launch LocalBlend form's conditions (blend_res <= height, width; height * width % 4
+    == 0; blend_res^2 <= 256; x, out, eps 16-byte aligned; no mask as well): P2P_E_ARG, before any
+    launch (no GPU is needed to be refused)."""
+    cls = _hip.PlmsArgs if entry == "p2p_plms_step" else _hip.LatentArgs
+    assert getattr(_hip.lib(), entry)(ctypes.byref(_step_args(cls, kw)), None) == -1
+
+
 def test_clock_probe_rejects():
     L = _hip.lib()
     assert L.p2p_clock_probe(None, 8, 1000, None) == -1

@@ -317,6 +317,15 @@ def test_store_scale(cuda):
     for steps in (7, 50, 3):
         y = _hip.store_scale(x, float(steps))
         assert torch.equal(y, x / steps)
+    # the scalar tail alone (n < 4), the tail after vectors, and a size past the grid cap of 4096
+    # blocks x 256 threads x 4 elements, where every thread strides; nothing is written past n
+    g = torch.Generator().manual_seed(313)
+    for n in (1, 3, 4, 5, 1023, 4 * 256 * 4096 + 7):
+        x = torch.randn(n, generator=g).to(cuda)
+        buf = torch.full((n + 8,), float("nan"), device=cuda)
+        y = _hip.store_scale(x, 7.0, buf[:n])
+        assert torch.equal(y, x / 7), n
+        assert bool(torch.isnan(buf[n:]).all()), n
 
 
 def _edit_mapper(B, K, weight=0.5):

@@ -10,6 +10,7 @@ ddim_prev / ddim_next on CPU in tests/test_oracle.py.
 import pytest
 import torch
 
+from blend_ref import blend_mask_ref
 from oracle import control as oc
 from p2p_amd import _hip, controllers
 from p2p_amd.ddim import DDIMScheduler
@@ -24,7 +25,9 @@ def sched():
     return s
 
 
-def eager(eps, x, coeffs, guidance, mask):
+def eager(eps, x, coeffs, guidance, mask, group_size=0, group_blend=None):
+    """group_size: prompts per prompt group (0: one group); every group blends towards its own
+    first prompt, if group_blend (one flag per group, None: all) says so."""
     dev = x.device
     sb, sa, sp, s1p = (torch.tensor(c, dtype=torch.float32, device=dev) for c in coeffs)
     if guidance is not None:
@@ -36,8 +39,14 @@ def eager(eps, x, coeffs, guidance, mask):
     out = sp * x0 + s1p * noise
     if mask is not None:
         m = mask[:, None].to(out.dtype)
-        out = out[:1] + m * (out - out[:1])
-        out = torch.cat([out[:1], out[1:]])
+        gs = group_size if group_size > 0 else out.shape[0]
+        parts = []
+        for g0 in range(0, out.shape[0], gs):
+            o = out[g0:g0 + gs]
+            if group_blend is None or group_blend[g0 // gs]:
+                o = o[:1] + m[g0:g0 + gs] * (o - o[:1])
+            parts.append(o)
+        out = torch.cat(parts)
     return out
 
 
@@ -54,6 +63,44 @@ def test_fused_prev_step_bit_exact(cuda, dtype, B, with_mask, t):
     got = _hip.latent_step(eps, x, torch.empty_like(x), coeffs, 7.5, mask)
     want = eager(eps, x, coeffs, 7.5, mask)
     assert want.dtype == torch.float32
+    assert torch.equal(got, want), (got - want).abs().max().item()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("shape", [(3, 5, 24, 40), (2, 1, 8, 8), (2, 4, 512, 512)], ids=lambda s: "x".join(map(str, s)))
+def test_mask_reading_step_other_shapes_bit_exact(cuda, dtype, shape):
+    """Away from 4 x 64 x 64: five channels on a non-square latent, a 64-element latent (a quarter
+    of one workgroup), and 1 M elements per prompt, where the 2048-block grid strides."""
+    B = shape[0]
+    g = torch.Generator().manual_seed(sum(shape))
+    eps = torch.randn(2 * B, *shape[1:], generator=g).to(dtype).to(cuda)
+    x = torch.randn(*shape, generator=g).to(cuda)
+    mask = (torch.rand(B, *shape[2:], generator=g) > 0.5).to(torch.uint8).to(cuda)
+    coeffs = sched().prev_coeffs(500)
+    for mk in (None, mask):
+        got = _hip.latent_step(eps, x, torch.full_like(x, float("nan")), coeffs, 7.5, mk)
+        want = eager(eps, x, coeffs, 7.5, mk)
+        assert torch.equal(got, want), (got - want).abs().max().item()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("gs,flags", [(2, (1, 1, 1)), (3, (1, 0, 1)), (4, (0, 1)), (1, (1, 1))],
+                         ids=["3x2_all", "3x3_on_off_on", "2x4_off_on", "2x1"])
+def test_mask_reading_step_groups_bit_exact(cuda, dtype, gs, flags):
+    """Several prompt groups: every group blends towards its own source prompt, and only where
+    group_blend says so (and with group_blend NULL, every group)."""
+    B = gs * len(flags)
+    g = torch.Generator().manual_seed(gs * 10 + len(flags))
+    eps = torch.randn(2 * B, 5, 24, 40, generator=g).to(dtype).to(cuda)
+    x = torch.randn(B, 5, 24, 40, generator=g).to(cuda)
+    mask = (torch.rand(B, 24, 40, generator=g) > 0.5).to(torch.uint8).to(cuda)
+    coeffs = sched().prev_coeffs(500)
+    gb = torch.tensor(flags, dtype=torch.uint8, device=cuda)
+    got = _hip.latent_step(eps, x, torch.full_like(x, float("nan")), coeffs, 7.5, mask, gs, gb)
+    want = eager(eps, x, coeffs, 7.5, mask, gs, flags)
+    assert torch.equal(got, want), (got - want).abs().max().item()
+    got = _hip.latent_step(eps, x, torch.full_like(x, float("nan")), coeffs, 7.5, mask, gs, None)
+    want = eager(eps, x, coeffs, 7.5, mask, gs, None)
     assert torch.equal(got, want), (got - want).abs().max().item()
 
 
@@ -147,29 +194,9 @@ def test_latent_step_builds_folded_blend_mask(cuda, dtype, sub, groups):
 
 
 def torch_blend_mask(sums, th_pool, th_sub, size, sub):
-    """null_text.py:41-67 restated in float64 torch on word sums that are already taken
-    (sums [B, 2, L*H, 256]: plane 0 the alpha words, plane 1 the substruct words): mean over the
-    L*H maps, 3x3 max-pool (alpha plane only), nearest upsample, max-normalise, threshold, then
-    mask[:1] + mask, and substruct: mask * ~(sub[:1] + sub).  Returns the mask and, per pixel, the
-    distance of the deciding normalised values from their thresholds."""
-    import torch.nn.functional as F
-
-    def plane(i, pool, th):
-        m = sums[:, i].double().mean(1).reshape(-1, 1, 16, 16)
-        if pool:
-            m = F.max_pool2d(m, (3, 3), (1, 1), padding=(1, 1))
-        m = F.interpolate(m, size=size)
-        m = (m / m.amax(dim=(2, 3), keepdim=True))[:, 0]
-        return m.gt(th), (m - th).abs()
-
-    mask, dist = plane(0, True, th_pool)
-    mask = mask[:1] | mask
-    dist = torch.minimum(dist, dist[:1])
-    if sub:
-        s, sd = plane(1, False, th_sub)
-        mask = mask & ~(s[:1] | s)
-        dist = torch.minimum(dist, torch.minimum(sd, sd[:1]))
-    return mask, dist
+    """null_text.py:41-67 restated in float64 torch on the 16x16 word sums [B, 2, L*H, 256]: the
+    helper the geometry tests share (tests/blend_ref.py), at the product's map resolution."""
+    return blend_mask_ref(sums, 16, th_pool, th_sub, size, sub)
 
 
 @pytest.mark.parametrize("sub", [False, True], ids=["nosub", "substruct"])
