@@ -391,6 +391,45 @@ typedef struct {
 
 int p2p_bias_residual(const p2p_bias_residual_args* a, p2p_stream_t stream);
 
+/* p2p_conv3x3: the resnets' 3x3 convolution (stride 1, padding 1, no bias; additive to ABI 16) as
+ * an implicit GEMM on the 16-bit MFMAs, under the glue's contract: f32 accumulation, one rounding
+ * at the store, no atomics, the same bits on every launch.  x is token-major [n, height * width,
+ * c_in] -- what p2p_group_norm writes with y_layout = P2P_LAYOUT_TOKENS -- `weight` the packed image
+ * p2p_conv3x3_pack makes of nn.Conv2d's [c_out, c_in, 3, 3] (once per model: [9, c_out, c_in]),
+ * y is NCHW [n, c_out, height * width].  Small maps split K over several workgroups per tile; their
+ * f32 partials go through `workspace` and are summed in a fixed order by a second launch.
+ * Rejected before any launch: a null x / weight / y, a size < 1, n * height * width (or an element
+ * count of x, y or the weights) beyond int32, a null workspace where the sizes need one (P2P_E_ARG);
+ * f32 (P2P_E_DTYPE); c_in % 32, c_out % 32, height * width % 8, a pointer off 16 bytes, and a size
+ * p2p_conv3x3_split answers 0 for (P2P_E_ALIGN: the caller runs its own convolution). */
+typedef struct {
+  const void* x;       /* [n, height * width, c_in]                                            */
+  const void* weight;  /* [9, c_out, c_in], from p2p_conv3x3_pack                              */
+  void* y;             /* [n, c_out, height * width]                                           */
+  float* workspace;    /* p2p_conv3x3_workspace_floats() f32; may be NULL where that is 0      */
+  int32_t n, height, width, c_in, c_out;
+  int32_t dtype;       /* P2P_DTYPE_BF16 / P2P_DTYPE_F16: x, weight and y                      */
+} p2p_conv3x3_args;
+
+int p2p_conv3x3(const p2p_conv3x3_args* a, p2p_stream_t stream);
+/* Workgroups along K per output tile for these sizes (a function of the sizes only): 1 = one launch,
+ * > 1 = the split form with its reduce launch, 0 = not served (a map above 64 x 64 pixels: not
+ * measured), or the P2P_E_* code p2p_conv3x3 answers for the sizes. */
+int p2p_conv3x3_split(int32_t n, int32_t height, int32_t width, int32_t c_in, int32_t c_out);
+/* f32 elements p2p_conv3x3 needs behind `workspace` (0 without a split), or the P2P_E_* code. */
+int64_t p2p_conv3x3_workspace_floats(int32_t n, int32_t height, int32_t width, int32_t c_in, int32_t c_out);
+
+/* packed[tap, co, ci] = weight[co, ci, tap / 3, tap % 3]: the K-major image p2p_conv3x3 stages.
+ * c_in % 32 and c_out % 32, packed on 16 bytes (else P2P_E_ALIGN). */
+typedef struct {
+  const void* weight;  /* [c_out, c_in, 3, 3], dense */
+  void* packed;        /* [9, c_out, c_in]           */
+  int32_t c_in, c_out;
+  int32_t dtype;
+} p2p_conv3x3_pack_args;
+
+int p2p_conv3x3_pack(const p2p_conv3x3_pack_args* a, p2p_stream_t stream);
+
 /* GEGLU: out[m, j] = in[m, j] * gelu(in[m, d + j]), j < d, gelu the exact erf form (F.gelu's
  * default).  Row strides in elements, multiples of 8 (as d), in_row_stride >= 2 d. */
 typedef struct {

@@ -441,6 +441,26 @@ int p2p_bias_residual(const p2p_bias_residual_args* a, p2p_stream_t stream) {
   return run_bias_residual(*a, (hipStream_t)stream);
 }
 
+int p2p_conv3x3(const p2p_conv3x3_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_conv3x3(*a, (hipStream_t)stream);
+}
+
+int p2p_conv3x3_split(int32_t n, int32_t height, int32_t width, int32_t c_in, int32_t c_out) {
+  const int rc = conv3x3_check_sizes(n, height, width, c_in, c_out);
+  return rc < 0 ? rc : select_conv3x3(n, height, width, c_in, c_out).split;
+}
+
+int64_t p2p_conv3x3_workspace_floats(int32_t n, int32_t height, int32_t width, int32_t c_in, int32_t c_out) {
+  const int rc = conv3x3_check_sizes(n, height, width, c_in, c_out);
+  return rc < 0 ? rc : conv3x3_workspace_floats(n, height, width, c_in, c_out);
+}
+
+int p2p_conv3x3_pack(const p2p_conv3x3_pack_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_conv3x3_pack(*a, (hipStream_t)stream);
+}
+
 int p2p_geglu(const p2p_geglu_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
   return run_geglu(*a, (hipStream_t)stream);

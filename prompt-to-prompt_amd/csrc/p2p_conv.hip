@@ -1,0 +1,301 @@
+// conv3x3_kernel: the resnets' 3x3 convolutions (stride 1, padding 1, no bias) as an implicit GEMM
+// on v_mfma_f32_16x16x32_{bf16,f16}.
+//
+//   M = n h w pixels (x is token-major: one pixel's channels are one contiguous K run),
+//   N = c_out, K = 9 c_in walked tap by tap: one K step is one tap and BK channels.
+//
+// A workgroup of four waves (2 x 2) owns a 128-pixel x BN-channel tile (BN = 128 or 160 = 4 or 5
+// 16-wide fragments per wave; every c_out of the U-Net is a multiple of 160).  Both operands are
+// staged through registers into one XOR-swizzled LDS image per step: the loads of step t + 1 are
+// issued before the MFMAs of step t and written after them, two barriers per step.  The halo is
+// made on the way from the staging registers to LDS: a tap that leaves the image (above / below, left / right -- which
+// covers the boundary between two images, since a tile's pixel index runs across them) loads the
+// pixel's own, always valid, address and is then replaced by zeros, so no load is conditional and
+// nothing is ever read out of bounds.
+//
+// Epilogue: the f32 accumulators are rounded once; a lane holds four consecutive pixels of one
+// output channel, the tile is transposed through LDS and stored NCHW in 16-byte pieces along the
+// pixels.  With a K split (small M) every split stores its f32 partial tile in NCHW order into the
+// caller's workspace and conv3x3_reduce_kernel sums the partials in split order: no atomics, the
+// same bits on every launch.
+#include "p2p_device.h"
+#include "p2p_kernels.h"
+
+namespace p2p {
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
+
+constexpr int kConvThreads = 256;
+constexpr int kTilePitch = kConvBM + 8;   // 16-bit elements per channel row of the epilogue's transposed tile
+
+struct ConvArgs {
+  const uint16_t* x;   // [n, h w, c_in]
+  const uint16_t* wp;  // [9, c_out, c_in]
+  void* y;             // [n, c_out, h w] 16-bit, or the f32 partials [split][n, c_out, h w]
+  int M, h, w, hw, c_in, c_out;
+  int m_tiles, n_tiles, split;
+};
+
+template <bool F16>
+__device__ __forceinline__ f32x4_t mma16(const u32x4_t& a, const u32x4_t& b, const f32x4_t& c) {
+  if constexpr (F16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0,
+                                                   0);
+}
+
+template <bool F16>
+__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
+  if constexpr (F16) return (uint32_t)f2h(lo) | ((uint32_t)f2h(hi) << 16);
+  else return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+}
+
+// byte offset of 16-byte chunk c of row r in a staged image with BK 16-bit elements per row: the
+// chunk index is XORed with the row so that the 16 rows one fragment read touches spread over the
+// banks (two rows per bank group instead of eight or sixteen)
+template <int BK>
+__device__ __forceinline__ int lds_chunk(int r, int c) {
+  constexpr int CPR = BK / 8;
+  const int s = BK == 64 ? (r & 7) : ((r >> 1) & 3);
+  return r * (BK * 2) + ((c ^ s) & (CPR - 1)) * 16;
+}
+
+// F16: f16 tensors (else bf16); BK: channels per K step; NF: 16-channel fragments per wave (BN = 32 NF);
+// PARTIAL: store the f32 partial of this block's K range instead of the rounded tile
+template <bool F16, int BK, int NF, bool PARTIAL>
+__global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(ConvArgs a) {
+  constexpr int BM = kConvBM, BN = 32 * NF;
+  constexpr int CPR = BK / 8;                 // 16-byte chunks per staged row
+  constexpr int RPP = kConvThreads / CPR;     // rows per staging pass
+  constexpr int NA = BM / RPP, NB = BN / RPP;
+  static_assert(BM % RPP == 0 && BN % RPP == 0, "staging passes cover the tiles exactly");
+  constexpr int kStage = (BM + BN) * BK * 2;
+  constexpr int kEpi = PARTIAL ? 0 : BN * kTilePitch * 2;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kStage > kEpi ? kStage : kEpi];
+  unsigned char* const ldsA = lds;
+  unsigned char* const ldsB = lds + BM * BK * 2;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int tiles = a.m_tiles * a.n_tiles;
+  int bid = blockIdx.x;
+  const int split = bid / tiles;          // slowest: a split's tiles are dispatched together
+  bid = xcd_remap(bid - split * tiles, tiles);
+  const int m0 = (bid / a.n_tiles) * BM, n0 = (bid % a.n_tiles) * BN;
+
+  const int steps_per_tap = a.c_in / BK;
+  const int steps = 9 * steps_per_tap;
+  const int t_begin = (int)((int64_t)steps * split / a.split), t_end = (int)((int64_t)steps * (split + 1) / a.split);
+
+  // staging roles: chunk sc of rows sr + RPP i
+  const int sc = tid % CPR, sr = tid / CPR;
+  int a_off[NA], a_yx[NA];     // element offset of the pixel's chunk; (py << 16 | px), or -1 past M
+  int a_lds[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const int r = sr + RPP * i;
+    int m = m0 + r;
+    const bool in = m < a.M;
+    m = in ? m : a.M - 1;
+    const int rem = m % a.hw;
+    const int py = rem / a.w, px = rem - py * a.w;
+    a_off[i] = m * a.c_in + sc * 8;
+    a_yx[i] = in ? ((py << 16) | px) : -1;
+    a_lds[i] = lds_chunk<BK>(r, sc);
+  }
+  int b_off[NB], b_lds[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int r = sr + RPP * i;
+    const int co = min(n0 + r, a.c_out - 1);   // rows past c_out repeat the last one; never stored
+    b_off[i] = co * a.c_in + sc * 8;
+    b_lds[i] = lds_chunk<BK>(r, sc);
+  }
+
+  u32x4_t ra[NA], rb[NB];
+  unsigned ra_ok = 0;          // bit i: ra[i] is inside its image (else write_step stores zeros)
+  auto load_step = [&](int t) {
+    const int tap = t / steps_per_tap;
+    const int c0 = (t - tap * steps_per_tap) * BK;
+    const int ky = tap / 3, dy = ky - 1, dx = tap - ky * 3 - 1;
+    const int shift = (dy * a.w + dx) * a.c_in;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int py = a_yx[i] >> 16, px = a_yx[i] & 0xffff;
+      const bool ok = (a_yx[i] >= 0) & ((unsigned)(py + dy) < (unsigned)a.h) & ((unsigned)(px + dx) < (unsigned)a.w);
+      ra[i] = *reinterpret_cast<const u32x4_t*>(a.x + (a_off[i] + c0 + (ok ? shift : 0)));
+      ra_ok = ok ? (ra_ok | (1u << i)) : (ra_ok & ~(1u << i));
+    }
+    const int wbase = tap * a.c_out * a.c_in + c0;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) rb[i] = *reinterpret_cast<const u32x4_t*>(a.wp + (wbase + b_off[i]));
+  };
+  auto write_step = [&]() {
+#pragma unroll
+    for (int i = 0; i < NA; ++i)   // the zeros are made here, behind the MFMAs, so that nothing waits for the load early
+      *reinterpret_cast<u32x4_t*>(ldsA + a_lds[i]) = ((ra_ok >> i) & 1u) ? ra[i] : u32x4_t{0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NB; ++i) *reinterpret_cast<u32x4_t*>(ldsB + b_lds[i]) = rb[i];
+  };
+
+  f32x4_t acc[4][NF];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  const int fr = lane & 15, fq = lane >> 4;
+  load_step(t_begin);
+  write_step();
+  __syncthreads();
+  for (int t = t_begin; t < t_end; ++t) {
+    const bool more = t + 1 < t_end;
+    if (more) load_step(t + 1);
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk) {
+      u32x4_t fa[4], fb[NF];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        fa[i] = *reinterpret_cast<const u32x4_t*>(ldsA + lds_chunk<BK>(wm * 64 + i * 16 + fr, kk * 4 + fq));
+#pragma unroll
+      for (int j = 0; j < NF; ++j)
+        fb[j] = *reinterpret_cast<const u32x4_t*>(ldsB + lds_chunk<BK>(wn * (16 * NF) + j * 16 + fr, kk * 4 + fq));
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) acc[i][j] = mma16<F16>(fa[i], fb[j], acc[i][j]);
+    }
+    __syncthreads();
+    if (more) {
+      write_step();
+      __syncthreads();
+    }
+  }
+
+  // acc[i][j][e]: pixel m0 + wm 64 + i 16 + fq 4 + e, channel n0 + wn 16 NF + j 16 + fr
+  if constexpr (PARTIAL) {
+    float* const ws = reinterpret_cast<float*>(a.y) + (int64_t)split * a.M * a.c_out;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm * 64 + i * 16 + fq * 4;
+      if (m >= a.M) continue;               // (M % 8 == 0: the four pixels stand or fall together)
+      const int img = m / a.hw, rem = m - img * a.hw;
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        const int co = n0 + wn * (16 * NF) + j * 16 + fr;
+        if (co < a.c_out) *reinterpret_cast<f32x4_t*>(ws + ((int64_t)img * a.c_out + co) * a.hw + rem) = acc[i][j];
+      }
+    }
+  } else {
+    // (the loop's last barrier stands behind every fragment read: the staging image may be reused)
+    uint16_t* const tile = reinterpret_cast<uint16_t*>(lds);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        const f32x4_t v = acc[i][j];
+        const u32x2_t p = {pack2<F16>(v[0], v[1]), pack2<F16>(v[2], v[3])};
+        *reinterpret_cast<u32x2_t*>(tile + (wn * (16 * NF) + j * 16 + fr) * kTilePitch + wm * 64 + i * 16 + fq * 4) = p;
+      }
+    __syncthreads();
+    uint16_t* const y = reinterpret_cast<uint16_t*>(a.y);
+    const int ch = tid & 15;                // 8-pixel piece of the tile's 128
+    const int m = m0 + ch * 8;
+    if (m < a.M) {
+      const int img = m / a.hw, rem = m - img * a.hw;   // hw % 8 == 0: a piece stays inside one image
+#pragma unroll
+      for (int p = 0; p < BN / 16; ++p) {
+        const int r = (tid >> 4) + 16 * p;
+        if (n0 + r < a.c_out)
+          *reinterpret_cast<u32x4_t*>(y + ((int64_t)img * a.c_out + n0 + r) * a.hw + rem) =
+              *reinterpret_cast<const u32x4_t*>(tile + r * kTilePitch + ch * 8);
+      }
+    }
+  }
+}
+
+// y = round(sum over the splits, in split order, of the f32 partials); 8 elements per thread
+template <bool F16>
+__global__ __launch_bounds__(256) void conv3x3_reduce_kernel(const float* ws, uint16_t* y, int64_t total, int split) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  if (i >= total) return;
+  f32x4_t s0 = *reinterpret_cast<const f32x4_t*>(ws + i), s1 = *reinterpret_cast<const f32x4_t*>(ws + i + 4);
+  for (int s = 1; s < split; ++s) {
+    s0 += *reinterpret_cast<const f32x4_t*>(ws + s * total + i);
+    s1 += *reinterpret_cast<const f32x4_t*>(ws + s * total + i + 4);
+  }
+  const u32x4_t o = {pack2<F16>(s0[0], s0[1]), pack2<F16>(s0[2], s0[3]), pack2<F16>(s1[0], s1[1]), pack2<F16>(s1[2], s1[3])};
+  *reinterpret_cast<u32x4_t*>(y + i) = o;
+}
+
+// packed[tap][co][ci] = w[co][ci][tap]
+__global__ __launch_bounds__(256) void conv3x3_pack_kernel(const uint16_t* w, uint16_t* packed, int c_in, int c_out) {
+  const int64_t per_tap = (int64_t)c_out * c_in;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= per_tap * 9) return;
+  const int tap = (int)(i / per_tap);
+  const int64_t r = i - tap * per_tap;     // co * c_in + ci
+  packed[i] = w[r * 9 + tap];
+}
+
+template <bool F16, int BK, int NF>
+void launch_conv_form(const ConvArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)(a.m_tiles * a.n_tiles * a.split));
+  if (a.split > 1) launch_kernel((conv3x3_kernel<F16, BK, NF, true>), grid, dim3(kConvThreads), 0, st, a);
+  else launch_kernel((conv3x3_kernel<F16, BK, NF, false>), grid, dim3(kConvThreads), 0, st, a);
+}
+
+template <bool F16>
+void launch_conv(const ConvArgs& a, const ConvPlan& plan, hipStream_t st) {
+  if (plan.bk == 64 && plan.bn == 160) launch_conv_form<F16, 64, 5>(a, st);
+  else if (plan.bk == 64) launch_conv_form<F16, 64, 4>(a, st);
+  else launch_conv_form<F16, 32, 4>(a, st);
+}
+
+bool conv_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+// the launcher: run_conv3x3 (p2p_dispatch.hip) has checked the arguments and chosen the plan
+int launch_conv3x3(const p2p_conv3x3_args& a, const ConvPlan& plan, hipStream_t st) {
+  ConvArgs k;
+  k.x = (const uint16_t*)a.x;
+  k.wp = (const uint16_t*)a.weight;
+  k.hw = a.height * a.width;
+  k.M = a.n * k.hw;
+  k.h = a.height, k.w = a.width, k.c_in = a.c_in, k.c_out = a.c_out;
+  k.m_tiles = (k.M + kConvBM - 1) / kConvBM;
+  k.n_tiles = (a.c_out + plan.bn - 1) / plan.bn;
+  k.split = plan.split;
+  k.y = plan.split > 1 ? (void*)a.workspace : a.y;
+  if (a.dtype == P2P_DTYPE_F16) launch_conv<true>(k, plan, st);
+  else launch_conv<false>(k, plan, st);
+  if (plan.split > 1) {
+    const int64_t total = (int64_t)k.M * a.c_out;   // % 8 == 0 (hw % 8 == 0)
+    const dim3 grid((unsigned)((total / 8 + 255) / 256));
+    if (a.dtype == P2P_DTYPE_F16)
+      launch_kernel(conv3x3_reduce_kernel<true>, grid, dim3(256), 0, st, (const float*)a.workspace, (uint16_t*)a.y, total,
+                    plan.split);
+    else
+      launch_kernel(conv3x3_reduce_kernel<false>, grid, dim3(256), 0, st, (const float*)a.workspace, (uint16_t*)a.y, total,
+                    plan.split);
+  }
+  return (int)hipGetLastError();
+}
+
+int run_conv3x3_pack(const p2p_conv3x3_pack_args& a, hipStream_t st) {
+  if (!a.weight || !a.packed) return P2P_E_ARG;
+  if (a.c_in < 1 || a.c_out < 1 || (int64_t)a.c_in * a.c_out * 9 > INT32_MAX) return P2P_E_ARG;
+  if (a.dtype != P2P_DTYPE_BF16 && a.dtype != P2P_DTYPE_F16) return P2P_E_DTYPE;
+  if (a.c_in % 32 || a.c_out % 32) return P2P_E_ALIGN;
+  if (((uintptr_t)a.weight & 1) || !conv_aligned16(a.packed)) return P2P_E_ALIGN;
+  const int64_t total = (int64_t)a.c_in * a.c_out * 9;
+  launch_kernel(conv3x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint16_t*)a.weight,
+                (uint16_t*)a.packed, a.c_in, a.c_out);
+  return (int)hipGetLastError();
+}
+
+}  // namespace p2p

@@ -1,4 +1,4 @@
-// run_self / run_cross: pick the kernel form (p2p_select.h) and hand it to its file's launcher.
+// run_self / run_cross / run_conv3x3: pick the kernel form (p2p_select.h) and hand it to its file's launcher.
 // Host code only; nothing here decides.
 #include "p2p_kernels.h"
 
@@ -25,6 +25,19 @@ int run_cross(const CrossArgs& a, int io_dtype, int compute, int d, hipStream_t 
   const CrossKernel k = (CrossKernel)sel;
   if (is_group(k)) return launch_cross_group(a, d, k, st);
   return launch_cross_entry(a, select_precision(io_dtype, compute), d, k, st);
+}
+
+int run_conv3x3(const p2p_conv3x3_args& a, hipStream_t st) {
+  if (!a.x || !a.weight || !a.y) return P2P_E_ARG;
+  const int rc = conv3x3_check_sizes(a.n, a.height, a.width, a.c_in, a.c_out);
+  if (rc == P2P_E_ARG) return rc;
+  if (a.dtype != P2P_DTYPE_BF16 && a.dtype != P2P_DTYPE_F16) return P2P_E_DTYPE;
+  if (rc < 0) return rc;
+  if (((uintptr_t)a.x | (uintptr_t)a.weight | (uintptr_t)a.y | (uintptr_t)a.workspace) & 15) return P2P_E_ALIGN;
+  const ConvPlan plan = select_conv3x3(a.n, a.height, a.width, a.c_in, a.c_out);
+  if (plan.split < 1) return P2P_E_ALIGN;   // a size the selection leaves to the caller's convolution
+  if (plan.split > 1 && !a.workspace) return P2P_E_ARG;
+  return launch_conv3x3(a, plan, st);
 }
 
 }  // namespace p2p

@@ -310,4 +310,62 @@ inline int select_cross(int io_dtype, int compute, int d, int n_groups, int H, i
   return (edit_dense && !edit_terms) ? CROSS_ENTRY_W4_DENSE : CROSS_ENTRY_W4;
 }
 
+// ---------------------------------------------------------------------------- 3x3 convolution
+// conv3x3_kernel (p2p_conv.hip): 128 pixels x bn output channels per workgroup, bk channels of one
+// tap per K step, `split` workgroups along K per tile (their f32 partials summed in split order by
+// conv3x3_reduce_kernel).  split == 0: the shape stays with the caller's convolution.
+constexpr int kConvBM = 128;
+constexpr int kConvMaxHW = 4096;     // the U-Net's largest map; the VAE's larger ones were not measured
+constexpr int kConvMaxSplit = 8;
+constexpr int kConvFillTiles = 512;  // two workgroups per CU of the 256
+constexpr int kConvMinSteps = 8;     // K steps a split keeps at least
+
+struct ConvPlan {
+  int bk, bn, split;
+};
+
+// sizes p2p_conv3x3 rejects before anything else: 0, or the P2P_E_* code
+inline int conv3x3_check_sizes(int n, int h, int w, int c_in, int c_out) {
+  if (n < 1 || h < 1 || w < 1 || c_in < 1 || c_out < 1) return P2P_E_ARG;
+  const int64_t m = (int64_t)n * h * w;
+  // pixels, and the element offsets into x, y and the packed weights, are 32-bit in the kernel
+  if (m > INT32_MAX || m * c_in > INT32_MAX || m * c_out > INT32_MAX || (int64_t)9 * c_in * c_out > INT32_MAX)
+    return P2P_E_ARG;
+  if (c_in % 32 || c_out % 32 || ((int64_t)h * w) % 8) return P2P_E_ALIGN;
+  return 0;
+}
+
+// Tile shape and K split from the sizes alone (never the device).  bk: 64 where it divides c_in, else
+// 32.  bn: 160 where it divides c_out (320, 640, 1280: no tail tile) and bk is 64, else 128.  split:
+// as many as bring the grid to kConvFillTiles workgroups (two per CU: the second hides the first
+// one's barriers), at most kConvMaxSplit -- each split writes and the reduce reads an f32 copy of y
+// -- and never leaving a split fewer than kConvMinSteps K steps.  At N = 8 that is 1 at 64x64 (512
+// tiles), 2 at 32x32, 4 at 16x16 and 8 at 8x8.  Measured (tools/conv_bench.py, profiles/r17/conv3x3/
+// conv_bench.txt): every resnet shape of the U-Net beats the chain it replaces, 1.74x to 2.38x; with
+// split 1 at 32x32 (256 tiles, one workgroup per CU) 640 -> 640 took 100.8 us against 83.4 with 2,
+// 1920 -> 640 291.9 against 217.6 (conv_bench_split1_at_32.txt).
+inline ConvPlan select_conv3x3(int n, int h, int w, int c_in, int c_out) {
+  ConvPlan p = {0, 0, 0};
+  if (conv3x3_check_sizes(n, h, w, c_in, c_out) != 0 || h * w > kConvMaxHW) return p;
+  p.bk = c_in % 64 == 0 ? 64 : 32;
+  p.bn = (p.bk == 64 && c_out % 160 == 0) ? 160 : 128;
+  const int64_t m = (int64_t)n * h * w;
+  const int64_t tiles = ((m + kConvBM - 1) / kConvBM) * ((c_out + p.bn - 1) / p.bn);
+  const int steps = 9 * c_in / p.bk;
+  int64_t s = 1;
+  if (tiles < kConvFillTiles) {
+    s = (kConvFillTiles + tiles - 1) / tiles;
+    if (s > kConvMaxSplit) s = kConvMaxSplit;
+    if (s > steps / kConvMinSteps) s = steps / kConvMinSteps;
+    if (s < 1) s = 1;
+  }
+  p.split = (int)s;
+  return p;
+}
+// f32 elements of p2p_conv3x3_args.workspace
+inline int64_t conv3x3_workspace_floats(int n, int h, int w, int c_in, int c_out) {
+  const ConvPlan p = select_conv3x3(n, h, w, c_in, c_out);
+  return p.split > 1 ? (int64_t)p.split * n * h * w * c_out : 0;
+}
+
 }  // namespace p2p

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 from typing import Optional, Sequence
 
 import torch
@@ -124,6 +125,21 @@ class BiasResidualArgs(ctypes.Structure):
         ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("bias2", ctypes.c_void_p),
         ("out", ctypes.c_void_p), ("n", ctypes.c_int32), ("channels", ctypes.c_int32), ("hw", ctypes.c_int32),
         ("b_layout", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
+class Conv3x3Args(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("y", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("n", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("c_in", ctypes.c_int32),
+        ("c_out", ctypes.c_int32), ("dtype", ctypes.c_int32),
+    ]
+
+
+class Conv3x3PackArgs(ctypes.Structure):
+    _fields_ = [
+        ("weight", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("c_in", ctypes.c_int32), ("c_out", ctypes.c_int32),
+        ("dtype", ctypes.c_int32),
     ]
 
 
@@ -263,7 +279,8 @@ def lib():
         other = {"p2p_error_string": ctypes.c_char_p, "p2p_source_hash": ctypes.c_char_p,
                  "p2p_self_attn_kernel": ctypes.c_char_p, "p2p_cross_attn_kernel": ctypes.c_char_p,
                  "p2p_attn_bwd_workspace": ctypes.c_int64, "p2p_group_norm_stats_floats": ctypes.c_int64,
-                 "p2p_group_norm_bwd_workspace_floats": ctypes.c_int64}
+                 "p2p_group_norm_bwd_workspace_floats": ctypes.c_int64,
+                 "p2p_conv3x3_workspace_floats": ctypes.c_int64}
         for fn in EXPORTED_SYMBOLS:
             getattr(L, fn).restype = other.get(fn, ctypes.c_int)
         L.p2p_error_string.argtypes = [ctypes.c_int]
@@ -284,6 +301,10 @@ def lib():
         L.p2p_group_norm_stats_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_bias_residual.argtypes = [ctypes.POINTER(BiasResidualArgs), vp]
         L.p2p_geglu.argtypes = [ctypes.POINTER(GegluArgs), vp]
+        L.p2p_conv3x3.argtypes = [ctypes.POINTER(Conv3x3Args), vp]
+        L.p2p_conv3x3_split.argtypes = [i32, i32, i32, i32, i32]
+        L.p2p_conv3x3_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
+        L.p2p_conv3x3_pack.argtypes = [ctypes.POINTER(Conv3x3PackArgs), vp]
         L.p2p_group_norm_bwd.argtypes = [ctypes.POINTER(GroupNormBwdArgs), vp]
         L.p2p_group_norm_bwd_workspace_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_geglu_bwd.argtypes = [ctypes.POINTER(GegluBwdArgs), vp]
@@ -333,7 +354,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_bias_quick_gelu", "p2p_text_attn_fwd", "p2p_bias_gelu", "p2p_maps_aggregate",
                     "p2p_map_panels", "p2p_null_loss", "p2p_null_adam", "p2p_group_norm_bwd",
                     "p2p_group_norm_bwd_workspace_floats", "p2p_geglu_bwd", "p2p_nchw_to_tokens", "p2p_time_embed",
-                    "p2p_time_proj")
+                    "p2p_time_proj", "p2p_conv3x3", "p2p_conv3x3_split", "p2p_conv3x3_workspace_floats",
+                    "p2p_conv3x3_pack")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -905,6 +927,87 @@ def bias_residual(a_nchw, b, bias=None, bias2=None, tokens: bool = False):
     r.dtype = _glue_dtype(a_nchw)
     ok = _glue_rc(lib().p2p_bias_residual(ctypes.byref(r), _stream(a_nchw.device)), "p2p_bias_residual")
     return out if ok else None
+
+
+# -- the resnets' 3x3 convolutions (p2p_conv.hip)
+def conv3x3_split(n: int, h: int, w: int, c_in: int, c_out: int) -> int:
+    """Workgroups along K per output tile that p2p_conv3x3 takes for these sizes (p2p_select.h): 1 =
+    one launch, above 1 = the split form, 0 or negative = the sizes are not served."""
+    return int(lib().p2p_conv3x3_split(n, h, w, c_in, c_out))
+
+
+class ConvWeights:
+    """The packed [9, C_out, C_in] images of nn.Conv2d 3x3 weights that p2p_conv3x3 stages (one
+    p2p_conv3x3_pack launch each), per convolution module, with what each was built from: the
+    weight's address, ``_version``, dtype and device.  ``get`` compares those on the host and repacks
+    when one has changed (an optimiser step, load_state_dict, ``.to()``) -- but never under graph
+    capture, where a miss returns None and the caller runs its own convolution: a captured graph must
+    not bake in a repack of weights that can change between replays.  The entries die with their
+    modules.  A packed image is a second copy of the weight."""
+
+    def __init__(self):
+        self._packed = weakref.WeakKeyDictionary()
+
+    @staticmethod
+    def key_of(w: torch.Tensor):
+        return (w.data_ptr(), w._version, w.dtype, w.device)
+
+    def get(self, conv) -> Optional[torch.Tensor]:
+        w = conv.weight
+        hit = self._packed.get(conv)
+        if hit is not None and hit[0] == self.key_of(w):
+            return hit[1]
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        packed = conv3x3_pack(w)
+        if packed is not None:
+            self._packed[conv] = (self.key_of(w), packed)
+        return packed
+
+
+CONV_WEIGHTS = ConvWeights()
+
+
+def conv3x3_pack(weight: torch.Tensor) -> Optional[torch.Tensor]:
+    """[9, C_out, C_in] from a dense [C_out, C_in, 3, 3] weight (p2p_conv3x3_pack), or None where the
+    kernel does not serve it (f32, CPU, a channel count that is no multiple of 32)."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or not weight.is_cuda or not weight.is_contiguous():
+        return None
+    c_out, c_in = weight.shape[:2]
+    with torch.no_grad():
+        packed = torch.empty((9, c_out, c_in), dtype=weight.dtype, device=weight.device)
+    a = Conv3x3PackArgs()
+    a.weight, a.packed = weight.data_ptr(), packed.data_ptr()
+    a.c_in, a.c_out = c_in, c_out
+    a.dtype = _glue_dtype(weight)
+    ok = _glue_rc(lib().p2p_conv3x3_pack(ctypes.byref(a), _stream(weight.device)), "p2p_conv3x3_pack")
+    return packed if ok else None
+
+
+def conv3x3(x_tokens: torch.Tensor, packed: torch.Tensor, h: int, w: int):
+    """F.conv2d(x, weight, None, 1, 1) as [N, C_out, H, W] (p2p_conv3x3) from the token-major
+    x_tokens [N, H*W, C_in] -- group_norm's ``tokens`` output -- and ``packed`` = conv3x3_pack(weight).
+    None where the library does not serve the operands; the caller runs its own convolution."""
+    _require_cuda(x_tokens, packed)
+    if x_tokens.dim() != 3 or packed.dim() != 3 or not x_tokens.is_contiguous() or not packed.is_contiguous() or \
+            packed.dtype != x_tokens.dtype:
+        return None
+    N, HW, c_in = x_tokens.shape
+    c_out = packed.shape[1]
+    if HW != h * w or packed.shape[0] != 9 or packed.shape[2] != c_in:
+        raise HipError(f"conv3x3: x {tuple(x_tokens.shape)} / weight {tuple(packed.shape)} / {h} x {w} do not match")
+    n_ws = int(lib().p2p_conv3x3_workspace_floats(N, h, w, c_in, c_out))
+    if n_ws < 0 or conv3x3_split(N, h, w, c_in, c_out) < 1:
+        return None
+    a = Conv3x3Args()
+    y = x_tokens.new_empty((N, c_out, h, w))
+    a.x, a.weight, a.y = x_tokens.data_ptr(), packed.data_ptr(), y.data_ptr()
+    if n_ws:
+        ws = torch.empty(n_ws, dtype=torch.float32, device=x_tokens.device)
+        a.workspace = ws.data_ptr()
+    a.n, a.height, a.width, a.c_in, a.c_out = N, h, w, c_in, c_out
+    a.dtype = _glue_dtype(x_tokens)
+    return y if _glue_rc(lib().p2p_conv3x3(ctypes.byref(a), _stream(x_tokens.device)), "p2p_conv3x3") else None
 
 
 def geglu(x):

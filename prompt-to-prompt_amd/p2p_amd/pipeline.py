@@ -256,7 +256,9 @@ class GraphedEditRunner:
 
     The graphs read the model's weights (and the stacked projection weights built from them) where
     they were at capture: after changing any weight, call release() -- the next batch of each size
-    then runs eagerly and captures again.
+    then runs eagerly and captures again.  The packed 3x3 convolution weights (_hip.ConvWeights)
+    follow the same rule: the eager first batch packs them, the graphs read the packed images, and
+    only an eager call notices a changed weight and repacks.
 
     Not captured: the text encoder (runs eagerly per batch, its output copied into the static
     context).  The cross K / V projections are captured in step 0's graph and read by the later

@@ -80,6 +80,40 @@ def _bias_residual(*args, **kw):
     return (unet_grad if torch.is_grad_enabled() else _hip).bias_residual(*args, **kw)
 
 
+# The resnets' 3x3 convolutions run on conv3x3_kernel (csrc/p2p_conv.hip) where p2p_select.h serves
+# the shape (A/B switch, read once: 0 = MIOpen's convolution everywhere)
+CONV_HIP = os.environ.get("P2P_CONV", "1") != "0"
+
+
+def _conv3x3_packed(conv: nn.Conv2d, x):
+    """The packed weight of ``conv`` where the HIP kernel takes conv(norm(x)) for x [N, C, H, W], else
+    None: the switch off, a map the selection does not serve, or no packed weight to be had (a miss
+    of the cache under graph capture)."""
+    if not CONV_HIP:
+        return None
+    N, _, H, W = x.shape
+    if _hip.conv3x3_split(N, H, W, conv.in_channels, conv.out_channels) < 1:
+        return None
+    return _hip.CONV_WEIGHTS.get(conv)
+
+
+def _norm_act_conv(norm: nn.GroupNorm, conv: nn.Conv2d, x, hip: bool = True, **kw):
+    """conv(silu(norm(x))) without conv's bias: the norm token-major into conv3x3_kernel where that
+    serves the shape (and ``hip`` allows it), else the NCHW norm and the module's own convolution.
+    None where the norm kernel does not serve x."""
+    packed = _conv3x3_packed(conv, x) if hip else None
+    if packed is not None:
+        if torch.is_grad_enabled():
+            y = unet_grad.group_norm_conv3x3(x, norm.weight, norm.bias, norm.num_groups, norm.eps, packed, conv.weight, **kw)
+        else:
+            h = _norm_act(norm, x, silu=True, tokens=True, **kw)
+            y = None if h is None else _hip.conv3x3(h, packed, x.shape[2], x.shape[3])
+        if y is not None:
+            return y
+    h = _norm_act(norm, x, silu=True, **kw)
+    return None if h is None else conv._conv_forward(h, conv.weight, None)
+
+
 class CrossAttention(nn.Module):
     def __init__(self, query_dim, context_dim=None, heads=8, dim_head=64, dropout=0.0):
         super().__init__()
@@ -228,6 +262,8 @@ class ResnetBlock2D(nn.Module):
         # temb_ch None: the VAE's resnets (vae.py), which take no time embedding and have no projection
         if temb_ch is not None:
             self.time_emb_proj = nn.Linear(temb_ch, out_ch)
+        # conv3x3_kernel was measured on the U-Net's shapes only: the VAE's resnets keep MIOpen
+        self._conv_hip = temb_ch is not None
         self.norm2 = nn.GroupNorm(groups, out_ch, eps=eps)
         self.conv2 = nn.Conv2d(out_ch, out_ch, 3, padding=1)
         self.conv_shortcut = nn.Conv2d(in_ch, out_ch, 1) if in_ch != out_ch else None
@@ -235,20 +271,20 @@ class ResnetBlock2D(nn.Module):
     def _forward_fused(self, x, temb, proj=None):
         """Both norms with their SiLU in one launch each; the convs run without bias: conv1's and
         the time embedding are added on load by norm2, conv2's and the shortcut's by the residual.
+        Where conv3x3_kernel serves a convolution's shape the norm in front of it writes token-major
+        and the kernel reads that (``_norm_act_conv``); elsewhere the NCHW norm and MIOpen.
         ``proj``: this block's time_emb_proj(F.silu(temb)) where the U-Net has computed it already."""
         c1, c2, sc = self.conv1, self.conv2, self.conv_shortcut
-        h = _norm_act(self.norm1, x, silu=True)
+        h = _norm_act_conv(self.norm1, c1, x, hip=self._conv_hip)
         if h is None:
             return None
-        h = c1._conv_forward(h, c1.weight, None)
         if proj is not None:
             chan_add = proj
         else:
             chan_add = self.time_emb_proj(F.silu(temb)) if temb is not None else None
-        h = _norm_act(self.norm2, h, silu=True, chan_add=chan_add, chan_bias=c1.bias)
+        h = _norm_act_conv(self.norm2, c2, h, hip=self._conv_hip, chan_add=chan_add, chan_bias=c1.bias)
         if h is None:
             return None
-        h = c2._conv_forward(h, c2.weight, None)
         if sc is not None:
             return _bias_residual(sc._conv_forward(x, sc.weight, None), h, c2.bias, sc.bias)
         return _bias_residual(x, h, c2.bias)

@@ -12,6 +12,11 @@ LayerNorm (the transformer blocks') has no HIP backward: ``_LayerNorm`` runs the
 forward, so that the autograd and no-grad forwards share their bits, and takes torch's gradient of
 F.layer_norm at the saved sum.
 
+The 3x3 convolution (csrc/p2p_conv.hip) has no HIP backward either: ``_GroupNormConv3x3`` runs the
+token-major p2p_group_norm and p2p_conv3x3 forward -- the bits of the no-grad forward again -- and
+takes torch's own input gradient of the convolution from the weight and dy into p2p_group_norm_bwd;
+the convolution's input is not saved.
+
 The wrappers return None where the forward binding reports the input unsupported, as the bindings
 do; a backward binding that rejects what its forward served raises ``HipError``.
 """
@@ -116,6 +121,36 @@ class _LayerNorm(torch.autograd.Function):
         return (g if ctx.needs_input_grad[0] else None), (g if ctx.needs_input_grad[1] else None), None, None, None
 
 
+class _GroupNormConv3x3(torch.autograd.Function):
+    """conv3x3(silu(GroupNorm(x + adds))) on the token-major p2p_group_norm and p2p_conv3x3: the bits of
+    the no-grad forward.  Backward: torch's input gradient of F.conv2d(., weight, padding=1)
+    (aten.convolution_backward with only the input mask set, from the weight and dy), which is NCHW,
+    handed to p2p_group_norm_bwd as an NCHW dy -- the gradient of the norm does not depend on the
+    layout its output was stored in, so nothing is transposed.  Saves what _GroupNorm saves and the
+    weight, not the normalised tokens; the weight gets no gradient (fused_glue_grad declines a
+    parameter that requires one)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, chan_add, chan_bias, groups, eps, packed, weight):
+        out = _hip.group_norm(x, gamma, beta, groups, eps, silu=True, tokens=True, chan_add=chan_add,
+                              chan_bias=chan_bias, return_stats=True)
+        y = None if out is None else _hip.conv3x3(out[0], packed, x.shape[2], x.shape[3])
+        if y is None:
+            raise _hip.HipError(f"group_norm + conv3x3 under autograd: {tuple(x.shape)} {x.dtype} is not served")
+        ctx.save_for_backward(x, out[1], gamma, beta, chan_add, chan_bias, weight)
+        ctx.groups = groups
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, stats, gamma, beta, chan_add, chan_bias, weight = ctx.saved_tensors
+        dh = torch.nn.grad.conv2d_input(tuple(x.shape), weight, dy.contiguous(), stride=1, padding=1)
+        dx = _hip.group_norm_bwd(dh.contiguous(), x, stats, gamma, beta, ctx.groups, silu=True, tokens=False,
+                                 chan_add=chan_add, chan_bias=chan_bias)
+        return dx, None, None, None, None, None, None, None, None
+
+
 def _dense16(x: torch.Tensor) -> bool:
     return x.dim() == 4 and x.is_contiguous()
 
@@ -129,6 +164,19 @@ def group_norm(x, gamma, beta, groups: int, eps: float, silu: bool = False, toke
     if not _dense16(x):
         return None
     return _GroupNorm.apply(x, gamma, beta, chan_add, chan_bias, int(groups), float(eps), bool(silu), bool(tokens))
+
+
+def group_norm_conv3x3(x, gamma, beta, groups: int, eps: float, packed, weight, chan_add=None, chan_bias=None):
+    """_hip.conv3x3 of the token-major _hip.group_norm (with SiLU) of x, differentiable with respect
+    to x; ``weight`` is the [C_out, C_in, 3, 3] tensor ``packed`` was made from.  None where a
+    binding does not serve the operands."""
+    if not x.requires_grad:
+        h = _hip.group_norm(x, gamma, beta, groups, eps, silu=True, tokens=True, chan_add=chan_add, chan_bias=chan_bias)
+        return None if h is None else _hip.conv3x3(h, packed, x.shape[2], x.shape[3])
+    if not _dense16(x) or packed.dtype != x.dtype or \
+            _hip.conv3x3_split(x.shape[0], x.shape[2], x.shape[3], x.shape[1], packed.shape[1]) < 1:
+        return None
+    return _GroupNormConv3x3.apply(x, gamma, beta, chan_add, chan_bias, int(groups), float(eps), packed, weight)
 
 
 def geglu(x):

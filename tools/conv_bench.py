@@ -1,0 +1,120 @@
+"""The resnets' 3x3 convolutions at the shapes the SD-v1.4 U-Net runs with N = 8: the chain a
+ResnetBlock2D ran before conv3x3_kernel (NCHW p2p_group_norm + SiLU, then MIOpen's convolution with
+its transposes, zero-fill and cast) against the chain it runs now (token-major p2p_group_norm, then
+p2p_conv3x3 and, where K is split, its reduce launch), and each convolution alone.  Every variant
+is captured into a HIP graph of --reps calls that rotate over enough operand sets to exceed the
+256 MB Infinity Cache, and the graph's replays are timed with events.  Random operands.  Prints one
+line per shape: microseconds per call (median of --iters replays), the kernel's TFLOP/s and its
+fraction of the 2500 TFLOP/s dense 16-bit peak, and the selection's K split.
+
+    python tools/conv_bench.py [--iters 15] [--reps 32] [--dtype bf16|f16] [--n 8]
+"""
+import argparse
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "prompt-to-prompt_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from p2p_amd import _hip  # noqa: E402
+
+PEAK_TFLOPS = 2500.0
+# (H = W, C_in, C_out, how many of the U-Net's resnet convolutions have the shape)
+SHAPES = [(64, 320, 320, 7), (64, 640, 320, 2), (64, 960, 320, 1),
+          (32, 320, 640, 1), (32, 640, 640, 6), (32, 960, 640, 1), (32, 1280, 640, 1), (32, 1920, 640, 1),
+          (16, 640, 1280, 1), (16, 1280, 1280, 6), (16, 1920, 1280, 1), (16, 2560, 1280, 2),
+          (8, 1280, 1280, 11), (8, 2560, 1280, 3)]
+
+
+def graph_us(fn, sets, reps, iters, dev):
+    """fn(i) enqueues one call on operand set i; microseconds per call from replays of a graph of reps calls."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for i in range(sets):
+            fn(i)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        for r in range(reps):
+            fn(r % sets)
+    times = []
+    for it in range(iters + 2):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        graph.replay()
+        e1.record()
+        e1.synchronize()
+        if it >= 2:
+            times.append(e0.elapsed_time(e1) * 1e3 / reps)
+    return sorted(times)[len(times) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=15)
+    ap.add_argument("--reps", type=int, default=32)
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
+    ap.add_argument("--n", type=int, default=8)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("conv_bench needs a GPU")
+    dev = torch.device("cuda:0")
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
+    _hip.lib()
+    _hip.check_source_hash()
+    N = args.n
+    g = torch.Generator(device=dev).manual_seed(0)
+    print(f"{torch.cuda.get_device_name(0)}, {args.dtype}, N = {N}, graphs of {args.reps} calls, median of {args.iters} replays")
+    print("us per call: [before] NCHW norm + MIOpen conv | MIOpen conv alone || [now] token norm + p2p_conv3x3 | "
+          "p2p_conv3x3 alone")
+    saved = 0.0
+    with torch.no_grad():
+        for res, cin, cout, count in SHAPES:
+            split = _hip.conv3x3_split(N, res, res, cin, cout)
+            per_set = N * res * res * (2 * cin + cout) * 2 + 2 * 9 * cin * cout * 2
+            sets = min(16, max(2, math.ceil(600e6 / per_set)))
+            xs = [torch.randn(N, cin, res, res, device=dev, generator=g).to(dtype) for _ in range(sets)]
+            ws = [(torch.randn(cout, cin, 3, 3, device=dev, generator=g) / math.sqrt(9 * cin)).to(dtype) for _ in range(sets)]
+            gamma, beta = torch.randn(cin, device=dev, generator=g).to(dtype), torch.randn(cin, device=dev, generator=g).to(dtype)
+            nchw = [_hip.group_norm(x, gamma, beta, 32, 1e-5, silu=True) for x in xs]
+            toks = [_hip.group_norm(x, gamma, beta, 32, 1e-5, silu=True, tokens=True) for x in xs]
+            packed = [_hip.conv3x3_pack(w) for w in ws]
+
+            def before(i):
+                return F.conv2d(_hip.group_norm(xs[i], gamma, beta, 32, 1e-5, silu=True), ws[i], None, 1, 1)
+
+            def miopen(i):
+                return F.conv2d(nchw[i], ws[i], None, 1, 1)
+
+            def now(i):
+                return _hip.conv3x3(_hip.group_norm(xs[i], gamma, beta, 32, 1e-5, silu=True, tokens=True), packed[i], res, res)
+
+            def ours(i):
+                return _hip.conv3x3(toks[i], packed[i], res, res)
+
+            variants = [before, miopen] + ([now, ours] if split >= 1 else [])
+            us = [graph_us(fn, sets, args.reps, args.iters, dev) for fn in variants]
+            gflop = 2.0 * N * res * res * 9 * cin * cout / 1e9
+            line = (f"  {res:2d}^2 {cin:4d} -> {cout:4d} (x{count:2d}) {gflop:6.1f} GFLOP  before {us[0]:7.1f} | {us[1]:7.1f} "
+                    f"({gflop / us[1] * 1e3:5.0f} TF)")
+            if split >= 1:
+                tf = gflop / us[3] * 1e3
+                line += (f" || now {us[2]:7.1f} | {us[3]:7.1f} ({tf:5.0f} TF, {100 * tf / PEAK_TFLOPS:4.1f} % of peak)  "
+                         f"split {split}  chain {us[0] / us[2]:.2f}x")
+                saved += count * (us[0] - us[2])
+            else:
+                line += " || not served by the selection"
+            print(line, flush=True)
+            del xs, ws, nchw, toks, packed
+    print(f"sum over the served convolutions of a U-Net call: {saved / 1e3:.2f} ms less per call")
+
+
+if __name__ == "__main__":
+    main()

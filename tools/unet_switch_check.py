@@ -5,7 +5,9 @@ process to process, profiles/r06/determinism_probe.log, and 50 DDIM steps amplif
 Two trees, or the two settings of P2P_FUSE_UNET, are compared by comparing their files:
     P2P_FUSE_UNET=0 python tools/unet_switch_check.py off.npy
     python tools/unet_switch_check.py off.npy --compare parent.npy      # prints max |delta|
---pkg DIR imports p2p_amd from another checkout's prompt-to-prompt_amd directory."""
+--pkg DIR imports p2p_amd from another checkout's prompt-to-prompt_amd directory.
+--vs-f32 prints, instead of writing a file, the distance of that forward to the same model run in
+float32, for the setting of the switches the process was started with (P2P_FUSE_UNET, P2P_CONV)."""
 import argparse
 import os
 import sys
@@ -19,6 +21,7 @@ def main():
     ap.add_argument("--pkg", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                   "prompt-to-prompt_amd"))
     ap.add_argument("--compare", default=None, help="an earlier file: print the distance instead of running")
+    ap.add_argument("--vs-f32", action="store_true", help="print the distance to the float32 model; `out` is a label")
     args = ap.parse_args()
     if args.compare:
         a, b = np.load(args.out), np.load(args.compare)
@@ -44,6 +47,14 @@ def main():
         again = model(x, 501, ctx)["sample"]
     torch.cuda.synchronize()
     assert torch.equal(y, again), "two forwards in one process differ: the check cannot tell anything"
+    if args.vs_f32:
+        with torch.no_grad():
+            ref = model.float()(x, 501, ctx)["sample"]
+        d = (y.float() - ref).abs()
+        print(f"{args.out}: fused glue {getattr(unet, 'FUSE_UNET', None)}, HIP conv3x3 {getattr(unet, 'CONV_HIP', None)}: "
+              f"against the f32 U-Net max |delta| {d.max().item():.4e}, mean {d.mean().item():.4e}, "
+              f"max |ref| {ref.abs().max().item():.3f}")
+        return
     np.save(args.out, y.float().cpu().numpy())
     print(f"{args.out}: fused glue {getattr(unet, 'FUSE_UNET', None)}, max |y| {y.abs().max().item():.3f}")
 
