@@ -333,6 +333,54 @@ typedef struct {
 
 int p2p_plms_step(const p2p_plms_step_args* a, p2p_stream_t stream);
 
+/* The same latent update for the DPM-Solver++ (2M) sampler (second-order multistep, data
+ * prediction: Lu et al. 2022, Algorithm 2; p2p_amd/dpm.py), additive to ABI 16:
+ *   e     = eps_u + guidance * (eps_c - eps_u)        (cfg = 1, rounded in eps_dtype as above;
+ *                                                      else e = eps), upcast to f32
+ *   m0    = (x - sigma_s * e) / alpha_s               (the data prediction; one IEEE division)
+ *   hist_out = m0                                     (nullable: NULL on the last call)
+ *   out   = x_coeff * x - m0_coeff * m0               (n_hist = 0: the first-order update)
+ *   out   = out - diff_coeff * (m0 - hist[0])         (n_hist = 1: the 2M term, hist[0] the
+ *                                                      previous call's m0)
+ * with, for the call at timestep s stepping to t (a = sqrt(alpha_cumprod), sg = sqrt(1 -
+ * alpha_cumprod), lambda = log a - log sg, h = lambda_t - lambda_s, r0 = (lambda_s - lambda_s') / h,
+ * s' the previous call's timestep): sigma_s = sg_s, alpha_s = a_s, x_coeff = sg_t / sg_s, m0_coeff =
+ * a_t * expm1(-h), diff_coeff = 0.5 * a_t * expm1(-h) / r0 -- the five host-side values of
+ * DPMSolverMultistepScheduler.plan_step, computed in double and rounded once to f32.  Then the
+ * LocalBlend blend of p2p_latent_step, in either form: mask / group_size / group_blend / blend_*
+ * mean what they mean there, with the same preconditions (in the blend_sums form also: hist[0] in
+ * use and hist_out 16-byte aligned).  hist[0], hist_out: f32 [B, C, H, W].  Every f32 operation is
+ * rounded to nearest, none contracted, so out and hist_out are bit-identical to
+ * DPMSolverMultistepScheduler.step on the same inputs.
+ * Rejected with P2P_E_ARG before any launch: a NULL eps / x / out, n_hist outside 0..1, a NULL
+ * hist[0] with n_hist = 1, hist_out equal to hist[0] in use or to x or out, alpha_s == 0, and what
+ * p2p_latent_step rejects (its geometry and, as there and in p2p_plms_step, a misaligned pointer of
+ * the blend_sums form: none of the three step forms answers P2P_E_ALIGN); P2P_E_DTYPE: an unknown
+ * eps_dtype. */
+typedef struct {
+  const void* eps;
+  int32_t eps_dtype;               /* P2P_DTYPE_*                                      */
+  int32_t cfg;
+  float guidance;
+  const float* x;
+  float* out;                      /* may alias x (not in the blend_sums form)         */
+  int32_t n_prompts, channels, height, width;
+  const uint8_t* mask;
+  int32_t group_size;
+  const uint8_t* group_blend;
+  const float* blend_sums[P2P_MAX_GROUPS];
+  int32_t blend_lh;
+  int32_t blend_res;
+  float blend_th_pool, blend_th_sub;
+  int32_t blend_sub;
+  const float* hist[1];            /* the previous call's data prediction              */
+  int32_t n_hist;                  /* 0 or 1                                           */
+  float* hist_out;                 /* NULL, or f32 [B, C, H, W]: this call's m0        */
+  float sigma_s, alpha_s, x_coeff, m0_coeff, diff_coeff;
+} p2p_dpm_step_args;
+
+int p2p_dpm_step(const p2p_dpm_step_args* a, p2p_stream_t stream);
+
 /* AttentionStore.get_average_attention (main.py:144-149): dst = src / divisor, computed as
  * src * (1.0f / divisor) -- what torch does for `cuda_tensor / python_scalar` on the
  * reference's cuda:0 device. */

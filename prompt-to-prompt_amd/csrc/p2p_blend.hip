@@ -392,9 +392,47 @@ struct PlmsC {
   }
 };
 
+// The DPM-Solver++ (2M) step (DPMSolverMultistepScheduler.step, p2p_amd/dpm.py; include/p2p_hip.h
+// p2p_dpm_step): the data prediction m0 = (x - sigma_s e) / alpha_s from the CFG-combined eps upcast
+// to f32 (m0 is what the scheduler's history keeps), the first-order update x_coeff x - m0_coeff m0
+// and, with the previous call's m1, the second-order term - diff_coeff (m0 - m1) -- f32, every
+// operation rounded on its own, in dpm.py's order
+template <typename P>
+__device__ __forceinline__ float dpm_update(const P& p, float e, float m1, float x, float& m0) {
+  m0 = __fdiv_rn(sub_rn(x, mul_rn(p.sigma_s, e)), p.alpha_s);
+  float o = sub_rn(mul_rn(p.x_coeff, x), mul_rn(p.m0_coeff, m0));
+  if (p.n_hist) o = sub_rn(o, mul_rn(p.diff_coeff, sub_rn(m0, m1)));
+  return o;
+}
+
+// the DPM step's scalars and history pointer by value (see DdimC).  The launcher points hist at x
+// when n_hist = 0, so the history load of an element is valid and unconditional
+struct DpmC {
+  int cfg, n_hist;
+  float guidance, sigma_s, alpha_s, x_coeff, m0_coeff, diff_coeff;
+  const float* hist;
+  float* hist_out;
+  __device__ explicit DpmC(const p2p_dpm_step_args& a)
+      : cfg(a.cfg), n_hist(a.n_hist), guidance(a.guidance), sigma_s(a.sigma_s), alpha_s(a.alpha_s),
+        x_coeff(a.x_coeff), m0_coeff(a.m0_coeff), diff_coeff(a.diff_coeff), hist(a.hist[0]), hist_out(a.hist_out) {}
+  struct Extra { f32x4_t h; };
+  __device__ __forceinline__ void load(Extra& e, int64_t idx) const {
+    e.h = *reinterpret_cast<const f32x4_t*>(hist + idx);
+  }
+  __device__ __forceinline__ void store(int64_t idx, const f32x4_t& m0) const {
+    if (hist_out) *reinterpret_cast<f32x4_t*>(hist_out + idx) = m0;
+  }
+  // kept: the value the history receives -- this element's data prediction
+  template <int DT>
+  __device__ __forceinline__ float from(float eu, float ec, float x, const Extra& e, int j, float& kept) const {
+    return dpm_update(*this, cfg_noise<DT>(*this, eu, ec), e.h[j], x, kept);
+  }
+};
+
 template <typename A> struct StepOf;
 template <> struct StepOf<p2p_latent_step_args> { using C = DdimC; };
 template <> struct StepOf<p2p_plms_step_args> { using C = PlmsC; };
+template <> struct StepOf<p2p_dpm_step_args> { using C = DpmC; };
 
 template <int DT, typename A>
 __device__ __forceinline__ float eps_at(const A& a, int64_t idx) {
@@ -426,7 +464,21 @@ __device__ __forceinline__ float step_prev(const p2p_plms_step_args& a, int b, i
   return plms_transfer(a, e, h, a.x[idx]);
 }
 
-// A: p2p_latent_step_args (DDIM) or p2p_plms_step_args -- the step form is step_prev's overload.
+// the same for the DPM-Solver++ step, which keeps the new data prediction (hist_out)
+template <int DT>
+__device__ __forceinline__ float step_prev(const p2p_dpm_step_args& a, int b, int64_t i, int64_t chw) {
+  const int64_t idx = (int64_t)b * chw + i;
+  const float eu = eps_at<DT>(a, idx);
+  const float ec = a.cfg ? eps_at<DT>(a, (int64_t)(a.n_prompts + b) * chw + i) : 0.f;
+  const float m1 = a.n_hist ? a.hist[0][idx] : 0.f;
+  float m0;
+  const float prev = dpm_update(a, cfg_noise<DT>(a, eu, ec), m1, a.x[idx], m0);
+  if (a.hist_out) a.hist_out[idx] = m0;
+  return prev;
+}
+
+// A: p2p_latent_step_args (DDIM), p2p_plms_step_args or p2p_dpm_step_args -- the step form is
+// step_prev's overload.
 // (This body and latent_blend_kernel's stay in the kernels: moved into an inlined device function,
 // hipcc no longer folds the block size with the launch bounds and schedules the DDIM instantiations
 // differently; templated on the argument struct their ISA is the one-form kernels'.)
@@ -464,7 +516,8 @@ __global__ __launch_bounds__(256) void latent_step_kernel(A a, int64_t chw) {
 // issues its eps / x loads (4 pixels x 1 channel, for b and the source) before the mask build's,
 // so the launch waits about two memory round trips; 64 workgroups keep the per-thread DDIM
 // arithmetic (two IEEE divisions per element) short.  The PLMS form (A = p2p_plms_step_args) adds
-// its four history loads per prompt to the same batch of loads and one store of the new eps.
+// its four history loads per prompt to the same batch of loads and one store of the new eps; the
+// DPM-Solver++ form (A = p2p_dpm_step_args) adds one history load and one store of the new x0.
 template <int DT, typename A>
 __global__ __launch_bounds__(256, 1) void latent_blend_kernel(A a, int64_t chw, int px_per_wg) {
   // every field this kernel reads, copied to scalars first (see DdimC)
@@ -573,30 +626,36 @@ static int check_latent_args(const A& a, bool& fused) {
 
 constexpr int kLatentPx = 256;    // latent pixels per workgroup (x 4 channels: 256 threads x 4 elements)
 
-int run_latent_step(const p2p_latent_step_args& a, hipStream_t st) {
-  bool fused = false;
-  if (const int rc = check_latent_args(a, fused)) return rc;
+// the launch both kernels' step forms share: the one-launch LocalBlend (fused) or the plain / mask form
+template <typename A>
+static int launch_latent_form(const A& a, bool fused, hipStream_t st) {
   const int64_t chw = (int64_t)a.channels * a.height * a.width;
   if (fused) {
     const int hw = a.height * a.width;
     dim3 grid((hw + kLatentPx - 1) / kLatentPx, a.n_prompts);
     if (a.eps_dtype == P2P_DTYPE_BF16)
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_BF16, p2p_latent_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_BF16, A>, grid, dim3(256), 0, st, a, chw, kLatentPx);
     else if (a.eps_dtype == P2P_DTYPE_F16)
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_F16, p2p_latent_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_F16, A>, grid, dim3(256), 0, st, a, chw, kLatentPx);
     else
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_F32, p2p_latent_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
+      launch_kernel(latent_blend_kernel<P2P_DTYPE_F32, A>, grid, dim3(256), 0, st, a, chw, kLatentPx);
     return (int)hipGetLastError();
   }
   int64_t blocks = (chw + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (a.eps_dtype == P2P_DTYPE_BF16)
-    launch_kernel(latent_step_kernel<P2P_DTYPE_BF16, p2p_latent_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+    launch_kernel(latent_step_kernel<P2P_DTYPE_BF16, A>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
   else if (a.eps_dtype == P2P_DTYPE_F16)
-    launch_kernel(latent_step_kernel<P2P_DTYPE_F16, p2p_latent_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+    launch_kernel(latent_step_kernel<P2P_DTYPE_F16, A>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
   else
-    launch_kernel(latent_step_kernel<P2P_DTYPE_F32, p2p_latent_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
+    launch_kernel(latent_step_kernel<P2P_DTYPE_F32, A>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
   return (int)hipGetLastError();
+}
+
+int run_latent_step(const p2p_latent_step_args& a, hipStream_t st) {
+  bool fused = false;
+  if (const int rc = check_latent_args(a, fused)) return rc;
+  return launch_latent_form(a, fused, st);
 }
 
 int run_plms_step(const p2p_plms_step_args& in, hipStream_t st) {
@@ -614,27 +673,24 @@ int run_plms_step(const p2p_plms_step_args& in, hipStream_t st) {
   // the one-launch form loads all four history slots of an element unconditionally: the unused
   // ones read x (a valid f32 tensor of the same shape, 16-byte aligned), and are discarded
   for (int k = a.n_hist; k < 4; ++k) a.hist[k] = a.x;
-  const int64_t chw = (int64_t)a.channels * a.height * a.width;
-  if (fused) {
-    const int hw = a.height * a.width;
-    dim3 grid((hw + kLatentPx - 1) / kLatentPx, a.n_prompts);
-    if (a.eps_dtype == P2P_DTYPE_BF16)
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_BF16, p2p_plms_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
-    else if (a.eps_dtype == P2P_DTYPE_F16)
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_F16, p2p_plms_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
-    else
-      launch_kernel(latent_blend_kernel<P2P_DTYPE_F32, p2p_plms_step_args>, grid, dim3(256), 0, st, a, chw, kLatentPx);
-    return (int)hipGetLastError();
+  return launch_latent_form(a, fused, st);
+}
+
+int run_dpm_step(const p2p_dpm_step_args& in, hipStream_t st) {
+  bool fused = false;
+  if (const int rc = check_latent_args(in, fused)) return rc;
+  if (in.n_hist < 0 || in.n_hist > 1 || in.alpha_s == 0.f) return P2P_E_ARG;
+  if (in.hist_out && (in.hist_out == in.x || in.hist_out == in.out)) return P2P_E_ARG;
+  uintptr_t ptr_bits = (uintptr_t)in.hist_out;
+  if (in.n_hist) {
+    if (!in.hist[0] || in.hist[0] == in.hist_out) return P2P_E_ARG;
+    ptr_bits |= (uintptr_t)in.hist[0];
   }
-  int64_t blocks = (chw + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (a.eps_dtype == P2P_DTYPE_BF16)
-    launch_kernel(latent_step_kernel<P2P_DTYPE_BF16, p2p_plms_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
-  else if (a.eps_dtype == P2P_DTYPE_F16)
-    launch_kernel(latent_step_kernel<P2P_DTYPE_F16, p2p_plms_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
-  else
-    launch_kernel(latent_step_kernel<P2P_DTYPE_F32, p2p_plms_step_args>, dim3((unsigned)blocks), dim3(256), 0, st, a, chw);
-  return (int)hipGetLastError();
+  if (fused && ptr_bits % 16) return P2P_E_ARG;
+  p2p_dpm_step_args a = in;
+  // the one-launch form loads the history slot unconditionally (see run_plms_step)
+  if (!a.n_hist) a.hist[0] = a.x;
+  return launch_latent_form(a, fused, st);
 }
 
 int run_localblend(const p2p_blend_args& a, hipStream_t st) {

@@ -421,6 +421,11 @@ int p2p_plms_step(const p2p_plms_step_args* a, p2p_stream_t stream) {
   return run_plms_step(*a, (hipStream_t)stream);
 }
 
+int p2p_dpm_step(const p2p_dpm_step_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_dpm_step(*a, (hipStream_t)stream);
+}
+
 int p2p_store_scale(const float* src, float* dst, float divisor, int64_t n, p2p_stream_t stream) {
   if (!src || !dst) return P2P_E_ARG;
   return run_store_scale(src, dst, divisor, n, (hipStream_t)stream);

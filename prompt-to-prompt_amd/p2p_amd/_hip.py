@@ -110,6 +110,21 @@ class PlmsArgs(ctypes.Structure):
     ]
 
 
+class DpmArgs(ctypes.Structure):
+    _fields_ = [
+        ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("cfg", ctypes.c_int32),
+        ("guidance", ctypes.c_float), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("n_prompts", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("mask", ctypes.c_void_p), ("group_size", ctypes.c_int32), ("group_blend", ctypes.c_void_p),
+        ("blend_sums", ctypes.c_void_p * MAX_GROUPS), ("blend_lh", ctypes.c_int32), ("blend_res", ctypes.c_int32),
+        ("blend_th_pool", ctypes.c_float), ("blend_th_sub", ctypes.c_float), ("blend_sub", ctypes.c_int32),
+        ("hist", ctypes.c_void_p * 1), ("n_hist", ctypes.c_int32), ("hist_out", ctypes.c_void_p),
+        ("sigma_s", ctypes.c_float), ("alpha_s", ctypes.c_float), ("x_coeff", ctypes.c_float),
+        ("m0_coeff", ctypes.c_float), ("diff_coeff", ctypes.c_float),
+    ]
+
+
 class GroupNormArgs(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("chan_add", ctypes.c_void_p), ("chan_add_stride", ctypes.c_int64),
@@ -294,6 +309,7 @@ def lib():
         L.p2p_store_scale.argtypes = [vp, vp, f32, i64, vp]
         L.p2p_latent_step.argtypes = [ctypes.POINTER(LatentArgs), vp]
         L.p2p_plms_step.argtypes = [ctypes.POINTER(PlmsArgs), vp]
+        L.p2p_dpm_step.argtypes = [ctypes.POINTER(DpmArgs), vp]
         L.p2p_attn_fwd_lse.argtypes = [ctypes.POINTER(AttnTensors), vp, vp]
         L.p2p_attn_bwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
         L.p2p_attn_bwd_workspace.argtypes = [ctypes.POINTER(AttnTensors)]
@@ -355,7 +371,7 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_map_panels", "p2p_null_loss", "p2p_null_adam", "p2p_group_norm_bwd",
                     "p2p_group_norm_bwd_workspace_floats", "p2p_geglu_bwd", "p2p_nchw_to_tokens", "p2p_time_embed",
                     "p2p_time_proj", "p2p_conv3x3", "p2p_conv3x3_split", "p2p_conv3x3_workspace_floats",
-                    "p2p_conv3x3_pack")
+                    "p2p_conv3x3_pack", "p2p_dpm_step")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -618,7 +634,7 @@ def store_scale(src: torch.Tensor, divisor: float, out: Optional[torch.Tensor] =
 
 
 def _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, what):
-    """The fields p2p_latent_step_args and p2p_plms_step_args share (a: LatentArgs or PlmsArgs),
+    """The fields the three latent-step argument structs share (a: LatentArgs, PlmsArgs or DpmArgs),
     checked and filled; returns the bytes of folded word sums the launch reads (0: no ``blend``)."""
     _require_cuda(eps, x, out, mask)
     for t in (eps, x, out):
@@ -725,6 +741,39 @@ def plms_step(eps, x, out, plan, guidance=None, mask=None, group_size=0, group_b
     if obs is not None and hasattr(obs, "after_aux"):
         obs.after_aux(kind)
     _check(rc, "p2p_plms_step")
+    return out
+
+
+def dpm_step(eps, x, out, plan, guidance=None, mask=None, group_size=0, group_blend=None, blend=None,
+             hist=(), hist_out=None):
+    """Fused CFG + DPM-Solver++ (2M) step + LocalBlend blend (p2p_dpm_step): latent_step's arguments
+    with, in place of the DDIM coefficients, ``plan`` -- a dpm.StepPlan (n_hist, sigma_s, alpha_s,
+    x_coeff, m0_coeff, diff_coeff) -- and the scheduler's history: ``hist`` empty or the previous
+    call's f32 [B, C, H, W] data prediction, ``hist_out`` None or the f32 tensor that receives this
+    call's."""
+    a = DpmArgs()
+    sums_bytes = _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, "dpm_step")
+    n_hist = int(plan.n_hist)
+    if n_hist != len(hist) or n_hist > 1:
+        raise HipError(f"dpm_step: {len(hist)} history tensors for a plan of {n_hist}")
+    _require_cuda(hist_out, *hist)
+    for h in tuple(hist) + ((hist_out,) if hist_out is not None else ()):
+        if h.dtype != torch.float32 or not h.is_contiguous() or h.shape != x.shape:
+            raise HipError("dpm_step: history tensors must be contiguous f32 of the latent's shape")
+    a.hist[0] = hist[0].data_ptr() if n_hist else None
+    a.n_hist = n_hist
+    a.hist_out = hist_out.data_ptr() if hist_out is not None else None
+    a.sigma_s, a.alpha_s, a.x_coeff = float(plan.sigma_s), float(plan.alpha_s), float(plan.x_coeff)
+    a.m0_coeff, a.diff_coeff = float(plan.m0_coeff), float(plan.diff_coeff)
+    kind = "dpm_blend" if sums_bytes else "dpm_step"
+    obs = LAUNCH_OBSERVER
+    if obs is not None and hasattr(obs, "before_aux"):
+        obs.before_aux(kind, eps.numel() * eps.element_size() + (2 + n_hist + (hist_out is not None)) * x.numel() * 4 +
+                       (mask.numel() if mask is not None else 0) + sums_bytes)
+    rc = lib().p2p_dpm_step(ctypes.byref(a), _stream(x.device))
+    if obs is not None and hasattr(obs, "after_aux"):
+        obs.after_aux(kind)
+    _check(rc, "p2p_dpm_step")
     return out
 
 

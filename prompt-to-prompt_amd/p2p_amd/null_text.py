@@ -226,6 +226,10 @@ class NullInversion:
 
     def __init__(self, model, num_ddim_steps: int = NUM_DDIM_STEPS, guidance_scale: float = GUIDANCE_SCALE,
                  use_graphs: bool = True):
+        sched = model.scheduler
+        if not (hasattr(sched, "prev_step") and hasattr(sched, "next_step")):
+            raise TypeError(f"NullInversion inverts with DDIM only: {type(sched).__name__} has no prev_step / "
+                            f"next_step (build the model with scheduler='ddim')")
         self.model = model
         self.tokenizer = model.tokenizer
         self.num_ddim_steps = num_ddim_steps

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from .ddim import DDIMScheduler
+from .dpm import DPMSolverMultistepScheduler
 from .pndm import PNDMScheduler
 from .tokenizer import default_tokenizer
 from .unet import UNet2DConditionModel
@@ -35,9 +36,24 @@ class SyntheticTextEncoder(nn.Module):
         return (self.token[ids] + self.pos[None, : ids.shape[1]],)
 
 
+def make_scheduler(scheduler: str):
+    """The scheduler a model's ``scheduler`` argument names, with Stable Diffusion's beta schedule."""
+    if scheduler == "ddim":
+        return DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                             clip_sample=False, set_alpha_to_one=False)
+    if scheduler == "pndm":
+        return PNDMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                             set_alpha_to_one=False, skip_prk_steps=True, steps_offset=1)
+    if scheduler == "dpm":
+        return DPMSolverMultistepScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                                           solver_order=2, lower_order_final=True)
+    raise ValueError(f"scheduler {scheduler!r}: 'ddim', 'pndm' or 'dpm'")
+
+
 class SyntheticStableDiffusion:
-    """``scheduler``: "ddim" (null_text.py:16-20) or "pndm" (the PLMS sampler the v1.4 pipeline of
-    main.py:29 carries: skip_prk_steps, steps_offset 1).  ``unet_config``: keyword arguments of the
+    """``scheduler``: "ddim" (null_text.py:16-20), "pndm" (the PLMS sampler the v1.4 pipeline of
+    main.py:29 carries: skip_prk_steps, steps_offset 1) or "dpm" (DPM-Solver++ 2M, dpm.py: the
+    scheduler users swap in to sample in 20-25 steps).  ``unet_config``: keyword arguments of the
     U-Net in place of the SD-v1.4 shape (tests run a narrow one).  ``vae``: also build the
     random-init SD-shaped ``vae.AutoencoderKL`` (or, with ``vae_config``, one of those keyword
     arguments) in the U-Net's dtype, so that text2image_ldm_stable returns images and NullInversion
@@ -59,14 +75,7 @@ class SyntheticStableDiffusion:
         clip = text_encoder or text_encoder_config is not None
         # (the stand-in draws from a generator of its own: leaving it out moves no other weight)
         self.text_encoder = None if clip else SyntheticTextEncoder().to(self.device)
-        if scheduler == "ddim":
-            self.scheduler = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                                           clip_sample=False, set_alpha_to_one=False)
-        elif scheduler == "pndm":
-            self.scheduler = PNDMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                                           set_alpha_to_one=False, skip_prk_steps=True, steps_offset=1)
-        else:
-            raise ValueError(f"scheduler {scheduler!r}: 'ddim' or 'pndm'")
+        self.scheduler = make_scheduler(scheduler)
         self.vae = None
         if vae or vae_config is not None:
             from .vae import AutoencoderKL
@@ -87,7 +96,8 @@ class SyntheticLatentDiffusion:
     ptp_utils.py:98-126).  The ldm-text2im-large-256 U-Net is the SD topology with a 1280-d
     LDMBert context and a 32x32 latent (diffusers config -- external knowledge, not in the
     container), so every attention layer has P <= 1024 and main.py:131 stores all of them.
-    Random-init weights, DDIM scheduler; by default a seeded embedding-table "LDMBert" and no
+    Random-init weights, DDIM scheduler (``scheduler``: "ddim", "pndm" or "dpm", as for
+    SyntheticStableDiffusion); by default a seeded embedding-table "LDMBert" and no
     VQ-VAE (text2image_ldm then returns latents).  ``unet_config``: keyword arguments of the U-Net
     in place of that shape (tests run a narrow one).  ``bert``: build the random-init
     ``ldm_bert.LDMBertModel`` (or, with ``bert_config``, one of those keyword arguments) in the
@@ -99,7 +109,7 @@ class SyntheticLatentDiffusion:
     weights do not change with them."""
 
     def __init__(self, device="cuda", dtype=torch.float32, seed=0, unet_config=None, bert=False, bert_config=None,
-                 vqvae=False, vqvae_config=None):
+                 vqvae=False, vqvae_config=None, scheduler="ddim"):
         self.device = torch.device(device)
         self.tokenizer = default_tokenizer()
         torch.manual_seed(seed)
@@ -109,8 +119,7 @@ class SyntheticLatentDiffusion:
         ldm_bert = bert or bert_config is not None
         # (the stand-in draws from a generator of its own: leaving it out moves no other weight)
         self.bert = None if ldm_bert else SyntheticTextEncoder(dim=1280, seed=2).to(self.device)
-        self.scheduler = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                                       clip_sample=False, set_alpha_to_one=False)
+        self.scheduler = make_scheduler(scheduler)
         self.vqvae = None
         if ldm_bert:
             from .ldm_bert import LDMBertModel
@@ -156,9 +165,13 @@ def seed_latent(seed: int) -> torch.Tensor:
 
 def make_replace_controller(prompts: Sequence[str], num_steps: int = 50, cross_replace_steps=0.8,
                             self_replace_steps=0.4, blend_words=BLEND_WORDS, store_self_maps=False,
-                            device=None, blend_th=(.3, .3)):
+                            device=None, blend_th=(.3, .3), start_blend=0.2):
+    """``start_blend``: passed to null_text.LocalBlend, which -- as the reference does -- counts its
+    start in calls of the module constant NUM_DDIM_STEPS = 50 (the blend starts after
+    int(start_blend * 50) calls), whatever ``num_steps`` is.  A 20-step run that wants the blend to
+    start after 20 % of its own calls passes ``0.2 * 20 / 50``."""
     from . import null_text
-    lb = (null_text.LocalBlend(list(prompts), blend_words, th=blend_th, device=device)
+    lb = (null_text.LocalBlend(list(prompts), blend_words, start_blend=start_blend, th=blend_th, device=device)
           if blend_words is not None else None)
     ctrl = null_text.AttentionReplace(list(prompts), num_steps, cross_replace_steps=cross_replace_steps,
                                       self_replace_steps=self_replace_steps, local_blend=lb, device=device)

@@ -90,9 +90,10 @@ def view_images(images, num_rows=1, offset_ratio=0.02):
 
 # ------------------------------------------------------------------ sampling loop
 def diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource=False, t_unet=None):
-    """One CFG denoising step (ptp_utils.py:65-76).  With this library's DDIM or PNDM scheduler and a
-    controller whose step_callback is its own, the CFG combine, the scheduler's step and LocalBlend's
-    latent blend run as one HIP kernel (p2p_latent_step / p2p_plms_step) -- same result, bit for bit.
+    """One CFG denoising step (ptp_utils.py:65-76).  With this library's DDIM, PNDM or DPM-Solver++
+    scheduler and a controller whose step_callback is its own, the CFG combine, the scheduler's step and
+    LocalBlend's latent blend run as one HIP kernel (p2p_latent_step / p2p_plms_step / p2p_dpm_step) --
+    same result, bit for bit.
     ``t_unet``: the same timestep as a device tensor for the U-Net (a captured step must not copy
     a host timestep to the device); the scheduler keeps reading the host ``t``."""
     tu = t if t_unet is None else t_unet
@@ -113,10 +114,12 @@ def diffusion_step(model, controller, latents, context, t, guidance_scale, low_r
 
 def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale):
     from .ddim import DDIMScheduler
+    from .dpm import DPMSolverMultistepScheduler
     from .pndm import PNDMScheduler
     sched = model.scheduler
-    if not (isinstance(sched, (DDIMScheduler, PNDMScheduler)) and latents.is_cuda and latents.dtype == torch.float32
-            and eps_u.dtype in (torch.float32, torch.bfloat16, torch.float16) and hasattr(controller, "fused_step_mask")):
+    if not (isinstance(sched, (DDIMScheduler, PNDMScheduler, DPMSolverMultistepScheduler)) and latents.is_cuda
+            and latents.dtype == torch.float32 and eps_u.dtype in (torch.float32, torch.bfloat16, torch.float16)
+            and hasattr(controller, "fused_step_mask")):
         return None
     ok, mask_fn = controller.fused_step_mask()
     if not ok:
@@ -125,7 +128,7 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
         eps = torch.cat([eps_u, eps_c]).contiguous()
     x = latents.contiguous()
     out = torch.empty_like(x)
-    plms = isinstance(sched, PNDMScheduler)
+    plms, dpm = isinstance(sched, PNDMScheduler), isinstance(sched, DPMSolverMultistepScheduler)
     if plms:
         # the call's plan (pndm.plan_step, which the eager step executes too): the sample it steps
         # from -- call 0's on the corrector call, kept by reference, hence the fresh ``out`` -- the
@@ -133,20 +136,27 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
         plan = sched.plan_step(t)
         src = sched.step_source(plan, x).contiguous()
         hist, hist_out = sched.history(plan), sched.history_slot(plan, x)
+    elif dpm:
+        # dpm.plan_step likewise: the previous call's data prediction, if the plan reads it, and the
+        # ring buffer that receives this call's
+        plan = sched.plan_step(t)
+        src, hist, hist_out = x, sched.history(plan), sched.history_slot(plan, x)
     else:
         plan, src, hist, hist_out = None, x, (), None
     _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out)
     if plms:
         sched.commit(plan, hist_out, x)
+    elif dpm:
+        sched.commit(plan, hist_out)
     return out
 
 
 def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out):
-    """The step's mask (mask_fn's side effects included) and the one p2p_latent_step / p2p_plms_step
-    launch (``plan``: the PLMS call's plan, None for DDIM) that reads it."""
+    """The step's mask (mask_fn's side effects included) and the one p2p_latent_step / p2p_plms_step /
+    p2p_dpm_step launch (``plan``: the PLMS or DPM-Solver++ call's plan, None for DDIM) that reads it."""
     from . import _hip
+    from . import dpm as dpm_mod
     from .controllers import FoldedBlendMask, StepMask, as_mask, group_mask_tensor
-    plms = plan is not None
     size = tuple(x.shape[2:])
     step = mask_fn(size) if mask_fn is not None else StepMask([None], 0)
     if not isinstance(step, StepMask):     # a controller of the caller's own may return its one entry bare
@@ -168,16 +178,17 @@ def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, pla
         mask = as_mask(entries[0])
     else:
         mask, group_size, group_blend = group_mask_tensor(entries, group_size, size)
-    if not plms:
+    if plan is None:
         return _hip.latent_step(eps, x, out, sched.prev_coeffs(t), guidance_scale, mask, group_size, group_blend, blend)
-    return _hip.plms_step(eps, src, out, plan, guidance_scale, mask, group_size, group_blend, blend, hist, hist_out)
+    launch = _hip.dpm_step if isinstance(plan, dpm_mod.StepPlan) else _hip.plms_step
+    return launch(eps, src, out, plan, guidance_scale, mask, group_size, group_blend, blend, hist, hist_out)
 
 
 def _blend_launch_ok(x, out, eps, folded, more=()) -> bool:
     """The one-launch LocalBlend's preconditions (p2p_blend.hip run_latent_step, include/p2p_hip.h):
     whole 4-pixel vectors (H*W % 4 == 0), 16-byte aligned x / out / eps (and ``more``: the PLMS
-    history tensors), and a latent at least as large as the map resolution (the 3x3-pooled map is
-    nearest-upsampled onto it)."""
+    or DPM-Solver++ history tensors), and a latent at least as large as the map resolution (the
+    3x3-pooled map is nearest-upsampled onto it)."""
     H, W = x.shape[2], x.shape[3]
     res = int(round(folded.sums.shape[-1] ** 0.5))
     ptrs = x.data_ptr() | out.data_ptr() | eps.data_ptr()

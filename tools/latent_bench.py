@@ -5,6 +5,8 @@ B = 4 prompts, 4 x 64 x 64 latents, bf16 eps, folded word sums [4, 2, 40, 256]:
   plain     : p2p_latent_step without a blend
   plms_*    : the same two one-launch / plain forms of p2p_plms_step at a call >= 4 (three stored eps
               read, the new one written)
+then, one line per batch ([4, 4, 64, 64] and [32, 4, 64, 64]), p2p_dpm_step against p2p_plms_step in
+alternated rounds (plms_vs_dpm).
 Usage: python tools/latent_bench.py [iters]   (run under rocprofv3 --kernel-trace --stats for kernel times)"""
 import json
 import os
@@ -62,6 +64,53 @@ def main(iters=200):
                                                       hist=hist, hist_out=slot), iters)
     r["plms_plain_us"] = timed(lambda: _hip.plms_step(eps, x, out, plan, 7.5, None, hist=hist, hist_out=slot), iters)
     print(json.dumps({k: round(v, 2) for k, v in r.items()}), flush=True)
+    for groups in (1, 8):
+        print(json.dumps(plms_vs_dpm(dev, groups, iters)), flush=True)
+
+
+def plms_vs_dpm(dev, groups, iters, rounds=5):
+    """p2p_dpm_step (a second-order call: one stored x0 read, the new one written) against
+    p2p_plms_step (call 5: three stored eps read, the new one written) of the same build, on the
+    batch of ``groups`` edit groups, plain and one-launch LocalBlend form: ``rounds`` alternated
+    rounds of the four, median and range of the per-round means."""
+    import statistics
+    from p2p_amd.dpm import DPMSolverMultistepScheduler
+    from p2p_amd.pndm import PNDMScheduler
+    gs, H, L = 4, 8, 5
+    B = groups * gs
+    g = torch.Generator(device=dev).manual_seed(1)
+    eps = torch.randn(2 * B, 4, 64, 64, device=dev, generator=g).to(torch.bfloat16)
+    x = torch.randn(B, 4, 64, 64, device=dev, generator=g)
+    out = torch.empty_like(x)
+    maps = [torch.zeros(gs * H, 256, 77, device=dev) for _ in range(L)]
+    alpha = torch.ones(gs, 77, device=dev)
+    blend = [controllers.FoldedBlendMask(maps, H, alpha, None, 0.3, 0.3, (64, 64),
+                                         torch.rand(gs, 2, L * H, 256, device=dev, generator=g)).latent_entry()
+             for _ in range(groups)]
+    group_size = gs if groups > 1 else 0
+    p, d = PNDMScheduler(), DPMSolverMultistepScheduler()
+    p.set_timesteps(50)
+    d.set_timesteps(20)
+    for s, calls in ((p, 5), (d, 2)):
+        for t in s.timesteps.tolist()[:calls]:
+            s.step(torch.randn(B, 4, 64, 64, device=dev, generator=g), t, x)
+    pp, dp = p.plan_step(int(p.timesteps[5])), d.plan_step(int(d.timesteps[2]))
+    ph, ps, dh, ds = p.history(pp), p.history_slot(pp, x), d.history(dp), d.history_slot(dp, x)
+    assert pp.n_hist == 3 and dp.n_hist == 1
+    forms = {
+        "plms_plain": lambda: _hip.plms_step(eps, x, out, pp, 7.5, None, hist=ph, hist_out=ps),
+        "dpm_plain": lambda: _hip.dpm_step(eps, x, out, dp, 7.5, None, hist=dh, hist_out=ds),
+        "plms_blend": lambda: _hip.plms_step(eps, x, out, pp, 7.5, None, group_size, None, blend, hist=ph, hist_out=ps),
+        "dpm_blend": lambda: _hip.dpm_step(eps, x, out, dp, 7.5, None, group_size, None, blend, hist=dh, hist_out=ds),
+    }
+    times = {k: [] for k in forms}
+    for _ in range(rounds):
+        for k, fn in forms.items():
+            times[k].append(timed(fn, iters))
+    res = {"shape": [B, 4, 64, 64], "rounds": rounds, "iters": iters}
+    for k, v in times.items():
+        res[k + "_us"] = {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+    return res
 
 
 if __name__ == "__main__":
