@@ -381,6 +381,66 @@ typedef struct {
 
 int p2p_dpm_step(const p2p_dpm_step_args* a, p2p_stream_t stream);
 
+/* The DDIM latent update of p2p_latent_step for the edit loop of Direct Inversion (Ju et al. 2023,
+ * "Direct Inversion: Boosting Diffusion-based Editing with 3 Lines of Code"; p2p_amd/
+ * direct_inversion.py), additive to ABI 16: the update, then the LocalBlend blend, then
+ *   out[g0] = out[g0] + offset[g]         g0 the first prompt of prompt group g
+ * -- the order of the eager lines (diffusion_step with its step_callback, then the add on the source
+ * row): the blend of the rows b != g0 reads the un-offset out[g0].  Every field of
+ * p2p_latent_step_args means what it means there, in all three forms (no mask, `mask` with groups,
+ * blend_sums), with the same preconditions; offset is f32 [n_prompts / group_size, C, H, W], one row
+ * with group_size = 0.  out is bit-identical to p2p_latent_step followed by torch's add.
+ * Rejected with P2P_E_ARG before any launch: a NULL offset, an offset that overlaps x or out, and
+ * what p2p_latent_step rejects (n_prompts not a multiple of group_size among it; in the blend_sums
+ * form a misaligned pointer, offset included -- none of the four step forms answers P2P_E_ALIGN);
+ * P2P_E_DTYPE: an unknown eps_dtype. */
+typedef struct {
+  const void* eps;
+  int32_t eps_dtype;               /* P2P_DTYPE_*                                      */
+  int32_t cfg;
+  float guidance;
+  const float* x;
+  float* out;                      /* may alias x (not in the blend_sums form)         */
+  int32_t n_prompts, channels, height, width;
+  float sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev;
+  const uint8_t* mask;
+  int32_t group_size;
+  const uint8_t* group_blend;
+  const float* blend_sums[P2P_MAX_GROUPS];
+  int32_t blend_lh;
+  int32_t blend_res;
+  float blend_th_pool, blend_th_sub;
+  int32_t blend_sub;
+  const float* offset;             /* f32 [n_prompts / group_size, C, H, W]            */
+} p2p_direct_step_args;
+
+int p2p_direct_step(const p2p_direct_step_args* a, p2p_stream_t stream);
+
+/* Direct Inversion's offsets for R rows in one launch -- R timesteps of one image, or R images:
+ *   rec[r]    = prev_step(eps_u[r] + guidance * (eps_c[r] - eps_u[r]), x[r])   with coef[r]
+ *   offset[r] = target[r] - rec[r]
+ * eps [2R, n] in eps_dtype (uncond block first), x / target / offset f32 [R, n] (n = C * H * W),
+ * coef f32 [R, 4] in DEVICE memory: row r's own sqrt(1 - a_t), sqrt(a_t), sqrt(a_prev),
+ * sqrt(1 - a_prev) (DDIMScheduler.prev_coeffs), since the rows may be different timesteps and a
+ * graph captured once is refilled per call.  Rounded as p2p_latent_step rounds (CFG products in
+ * the eps dtype, the rest in f32, nothing contracted): rec[r] is bit-identical to p2p_latent_step
+ * without a mask on row r with that row's coefficients, and offset[r] to torch's subtraction.
+ * Rejected before anything is launched: a null pointer, R <= 0 or n <= 0 (P2P_E_ARG); an unknown
+ * eps_dtype (P2P_E_DTYPE); R > 65535 (P2P_E_BATCH); n % 4 != 0, or eps / x / target / coef /
+ * offset off 16 bytes (P2P_E_ALIGN, the rules of p2p_null_loss). */
+typedef struct {
+  const void* eps;        /* [2R, n] in eps_dtype                                       */
+  int32_t eps_dtype;      /* P2P_DTYPE_F32 / P2P_DTYPE_BF16 / P2P_DTYPE_F16             */
+  float guidance;
+  const float* x;         /* [R, n] the trajectory latent at each row's timestep        */
+  const float* target;    /* [R, n] the next cleaner trajectory latent                  */
+  const float* coef;      /* [R, 4] f32, device                                         */
+  float* offset;          /* [R, n] out                                                 */
+  int32_t R, n;
+} p2p_direct_offset_args;
+
+int p2p_direct_offset(const p2p_direct_offset_args* a, p2p_stream_t stream);
+
 /* AttentionStore.get_average_attention (main.py:144-149): dst = src / divisor, computed as
  * src * (1.0f / divisor) -- what torch does for `cuda_tensor / python_scalar` on the
  * reference's cuda:0 device. */

@@ -312,7 +312,8 @@ __device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, 
 struct DdimC {
   int cfg;
   float guidance, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev;
-  __device__ explicit DdimC(const p2p_latent_step_args& a)
+  template <typename A>   // p2p_latent_step_args, or p2p_direct_step_args (the same fields)
+  __device__ explicit DdimC(const A& a)
       : cfg(a.cfg), guidance(a.guidance), sqrt_beta_t(a.sqrt_beta_t), sqrt_alpha_t(a.sqrt_alpha_t),
         sqrt_alpha_prev(a.sqrt_alpha_prev), sqrt_one_minus_alpha_prev(a.sqrt_one_minus_alpha_prev) {}
   // the step-form interface of latent_blend_kernel: DDIM reads no tensor beside eps and x
@@ -429,8 +430,16 @@ struct DpmC {
   }
 };
 
+// The Direct Inversion edit step (include/p2p_hip.h p2p_direct_step): the DDIM step, and after
+// the blend the group's offset row added to the group's source prompt
+struct DirectC : DdimC {
+  const float* offset;
+  __device__ explicit DirectC(const p2p_direct_step_args& a) : DdimC(a), offset(a.offset) {}
+};
+
 template <typename A> struct StepOf;
 template <> struct StepOf<p2p_latent_step_args> { using C = DdimC; };
+template <> struct StepOf<p2p_direct_step_args> { using C = DirectC; };
 template <> struct StepOf<p2p_plms_step_args> { using C = PlmsC; };
 template <> struct StepOf<p2p_dpm_step_args> { using C = DpmC; };
 
@@ -477,8 +486,20 @@ __device__ __forceinline__ float step_prev(const p2p_dpm_step_args& a, int b, in
   return prev;
 }
 
-// A: p2p_latent_step_args (DDIM), p2p_plms_step_args or p2p_dpm_step_args -- the step form is
-// step_prev's overload.
+// the DDIM step again for the Direct Inversion form (the offset is added by the kernels, after the blend)
+template <int DT>
+__device__ __forceinline__ float step_prev(const p2p_direct_step_args& a, int b, int64_t i, int64_t chw) {
+  const float eu = eps_at<DT>(a, (int64_t)b * chw + i);
+  const float ec = a.cfg ? eps_at<DT>(a, (int64_t)(a.n_prompts + b) * chw + i) : 0.f;
+  return ddim_from<DT>(a, eu, ec, a.x[(int64_t)b * chw + i]);
+}
+
+template <typename A>
+constexpr bool kDirectForm = std::is_same<A, p2p_direct_step_args>::value;
+
+// A: p2p_latent_step_args (DDIM), p2p_plms_step_args, p2p_dpm_step_args or p2p_direct_step_args --
+// the step form is step_prev's overload.  The Direct Inversion form adds offset[g] to group g's
+// source prompt as it is stored: prev0, which the group's other prompts blend towards, stays un-offset.
 // (This body and latent_blend_kernel's stay in the kernels: moved into an inlined device function,
 // hipcc no longer folds the block size with the launch bounds and schedules the DDIM instantiations
 // differently; templated on the argument struct their ISA is the one-form kernels'.)
@@ -498,6 +519,7 @@ __global__ __launch_bounds__(256) void latent_step_kernel(A a, int64_t chw) {
       if (bg == 0) {
         prev0 = prev;                                     // the group's source prompt
         blend = a.mask && (!a.group_blend || a.group_blend[b / gs]);
+        if constexpr (kDirectForm<A>) prev = add_rn(prev, a.offset[(int64_t)(b / gs) * chw + i]);
       } else if (blend) {
         const float m = a.mask[(int64_t)b * HW + yx] ? 1.f : 0.f;
         prev = add_rn(prev0, mul_rn(m, sub_rn(prev, prev0)));
@@ -517,7 +539,10 @@ __global__ __launch_bounds__(256) void latent_step_kernel(A a, int64_t chw) {
 // so the launch waits about two memory round trips; 64 workgroups keep the per-thread DDIM
 // arithmetic (two IEEE divisions per element) short.  The PLMS form (A = p2p_plms_step_args) adds
 // its four history loads per prompt to the same batch of loads and one store of the new eps; the
-// DPM-Solver++ form (A = p2p_dpm_step_args) adds one history load and one store of the new x0.
+// DPM-Solver++ form (A = p2p_dpm_step_args) adds one history load and one store of the new x0; the
+// Direct Inversion form (A = p2p_direct_step_args) one load of the group's offset row, which the
+// source prompt's workgroups add to what they store (the edit workgroups recompute the un-offset
+// source from the inputs, as before).
 template <int DT, typename A>
 __global__ __launch_bounds__(256, 1) void latent_blend_kernel(A a, int64_t chw, int px_per_wg) {
   // every field this kernel reads, copied to scalars first (see DdimC)
@@ -571,6 +596,8 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(A a, int64_t chw, 
       xv[s2] = *reinterpret_cast<const f32x4_t*>(xg + (int64_t)bb * chw + i);
       dc.load(ex[s2], (int64_t)bb * chw + i);
     }
+    f32x4_t offv = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (kDirectForm<A>) offv = *reinterpret_cast<const f32x4_t*>(dc.offset + (int64_t)g * chw + i);
     if (blend && c0 == 0) {
       const int R2 = res * res;
       build_blend_mask(ws, ws + (int64_t)bg * 2 * lh * R2, lh, res, H, W, th_pool, th_sub, use_sub != 0, L);
@@ -589,6 +616,8 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(A a, int64_t chw, 
         const float m = L.msrc[blend_src_of(px + j, res, H, W)];
         prev = add_rn(prev0, mul_rn(m, sub_rn(prev, prev0)));
       }
+      if constexpr (kDirectForm<A>)
+        if (bg == 0) prev = add_rn(prev, offv[j]);
       o[j] = prev;
     }
     *reinterpret_cast<f32x4_t*>(og + (int64_t)b * chw + (int64_t)c * HW + px) = o;
@@ -691,6 +720,80 @@ int run_dpm_step(const p2p_dpm_step_args& in, hipStream_t st) {
   // the one-launch form loads the history slot unconditionally (see run_plms_step)
   if (!a.n_hist) a.hist[0] = a.x;
   return launch_latent_form(a, fused, st);
+}
+
+int run_direct_step(const p2p_direct_step_args& a, hipStream_t st) {
+  bool fused = false;
+  if (!a.offset) return P2P_E_ARG;
+  if (const int rc = check_latent_args(a, fused)) return rc;
+  const int gs = a.group_size > 0 ? a.group_size : a.n_prompts;
+  const int64_t chw = (int64_t)a.channels * a.height * a.width;
+  const uintptr_t off0 = (uintptr_t)a.offset, off1 = off0 + (uintptr_t)(a.n_prompts / gs) * chw * 4;
+  const uintptr_t lat_bytes = (uintptr_t)a.n_prompts * chw * 4;
+  for (const uintptr_t p : {(uintptr_t)a.x, (uintptr_t)a.out})
+    if (off0 < p + lat_bytes && p < off1) return P2P_E_ARG;
+  if (fused && off0 % 16) return P2P_E_ARG;
+  return launch_latent_form(a, fused, st);
+}
+
+// ---------------------------------------------------------------- Direct Inversion offsets
+// offset[r] = target[r] - prev_step(cfg(eps_u[r], eps_c[r]), x[r]) for R rows, each with its own
+// DDIM coefficients read from device memory (include/p2p_hip.h p2p_direct_offset): grid (chunks of
+// 256 threads x 4 elements, R).  ddim_from is the latent step's, so a row's prev_step is that
+// kernel's bit for bit.
+struct OffsetC {
+  int cfg;
+  float guidance, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev;
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) void direct_offset_kernel(p2p_direct_offset_args a) {
+  const int r = blockIdx.y;
+  const int iv = blockIdx.x * 256 + threadIdx.x;      // 4-element piece of row r
+  if (iv >= a.n / 4) return;
+  const f32x4_t cv = reinterpret_cast<const f32x4_t*>(a.coef)[r];
+  const OffsetC c{1, a.guidance, cv[0], cv[1], cv[2], cv[3]};
+  const int64_t i = (int64_t)r * a.n + (int64_t)iv * 4;
+  const int64_t ic = (int64_t)(a.R + r) * a.n + (int64_t)iv * 4;
+  f32x4_t eu, ec;
+  if constexpr (DT == P2P_DTYPE_F32) {
+    eu = *reinterpret_cast<const f32x4_t*>(static_cast<const float*>(a.eps) + i);
+    ec = *reinterpret_cast<const f32x4_t*>(static_cast<const float*>(a.eps) + ic);
+  } else {
+    const uint2 ru = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(a.eps) + i);
+    const uint2 rc = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(a.eps) + ic);
+    auto widen = [](uint32_t v) { return DT == P2P_DTYPE_BF16 ? bf2f((uint16_t)v) : h2f((uint16_t)v); };
+    eu = f32x4_t{widen(ru.x & 0xffffu), widen(ru.x >> 16), widen(ru.y & 0xffffu), widen(ru.y >> 16)};
+    ec = f32x4_t{widen(rc.x & 0xffffu), widen(rc.x >> 16), widen(rc.y & 0xffffu), widen(rc.y >> 16)};
+  }
+  const f32x4_t xv = *reinterpret_cast<const f32x4_t*>(a.x + i);
+  const f32x4_t tv = *reinterpret_cast<const f32x4_t*>(a.target + i);
+  f32x4_t o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = sub_rn(tv[j], ddim_from<DT>(c, eu[j], ec[j], xv[j]));
+  *reinterpret_cast<f32x4_t*>(a.offset + i) = o;
+}
+
+constexpr int kOffsetMaxRows = 65535;   // grid.y
+
+int run_direct_offset(const p2p_direct_offset_args& a, hipStream_t st) {
+  if (!a.eps || !a.x || !a.target || !a.coef || !a.offset) return P2P_E_ARG;
+  if (a.R <= 0 || a.n <= 0) return P2P_E_ARG;
+  if (a.eps_dtype != P2P_DTYPE_F32 && a.eps_dtype != P2P_DTYPE_BF16 && a.eps_dtype != P2P_DTYPE_F16)
+    return P2P_E_DTYPE;
+  if (a.R > kOffsetMaxRows) return P2P_E_BATCH;
+  if (a.n % 4) return P2P_E_ALIGN;
+  // (four elements per access: 16 bytes of f32, 8 of a 16-bit eps, and every row starts on such a boundary)
+  if (((uintptr_t)a.eps | (uintptr_t)a.x | (uintptr_t)a.target | (uintptr_t)a.coef | (uintptr_t)a.offset) & 15)
+    return P2P_E_ALIGN;
+  const dim3 grid((unsigned)((a.n / 4 + 255) / 256), (unsigned)a.R);
+  if (a.eps_dtype == P2P_DTYPE_BF16)
+    launch_kernel(direct_offset_kernel<P2P_DTYPE_BF16>, grid, dim3(256), 0, st, a);
+  else if (a.eps_dtype == P2P_DTYPE_F16)
+    launch_kernel(direct_offset_kernel<P2P_DTYPE_F16>, grid, dim3(256), 0, st, a);
+  else
+    launch_kernel(direct_offset_kernel<P2P_DTYPE_F32>, grid, dim3(256), 0, st, a);
+  return (int)hipGetLastError();
 }
 
 int run_localblend(const p2p_blend_args& a, hipStream_t st) {

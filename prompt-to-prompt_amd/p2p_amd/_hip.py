@@ -125,6 +125,18 @@ class DpmArgs(ctypes.Structure):
     ]
 
 
+class DirectStepArgs(ctypes.Structure):
+    _fields_ = LatentArgs._fields_ + [("offset", ctypes.c_void_p)]
+
+
+class DirectOffsetArgs(ctypes.Structure):
+    _fields_ = [
+        ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("guidance", ctypes.c_float),
+        ("x", ctypes.c_void_p), ("target", ctypes.c_void_p), ("coef", ctypes.c_void_p), ("offset", ctypes.c_void_p),
+        ("R", ctypes.c_int32), ("n", ctypes.c_int32),
+    ]
+
+
 class GroupNormArgs(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("chan_add", ctypes.c_void_p), ("chan_add_stride", ctypes.c_int64),
@@ -310,6 +322,8 @@ def lib():
         L.p2p_latent_step.argtypes = [ctypes.POINTER(LatentArgs), vp]
         L.p2p_plms_step.argtypes = [ctypes.POINTER(PlmsArgs), vp]
         L.p2p_dpm_step.argtypes = [ctypes.POINTER(DpmArgs), vp]
+        L.p2p_direct_step.argtypes = [ctypes.POINTER(DirectStepArgs), vp]
+        L.p2p_direct_offset.argtypes = [ctypes.POINTER(DirectOffsetArgs), vp]
         L.p2p_attn_fwd_lse.argtypes = [ctypes.POINTER(AttnTensors), vp, vp]
         L.p2p_attn_bwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
         L.p2p_attn_bwd_workspace.argtypes = [ctypes.POINTER(AttnTensors)]
@@ -371,7 +385,7 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_map_panels", "p2p_null_loss", "p2p_null_adam", "p2p_group_norm_bwd",
                     "p2p_group_norm_bwd_workspace_floats", "p2p_geglu_bwd", "p2p_nchw_to_tokens", "p2p_time_embed",
                     "p2p_time_proj", "p2p_conv3x3", "p2p_conv3x3_split", "p2p_conv3x3_workspace_floats",
-                    "p2p_conv3x3_pack", "p2p_dpm_step")
+                    "p2p_conv3x3_pack", "p2p_dpm_step", "p2p_direct_step", "p2p_direct_offset")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -775,6 +789,51 @@ def dpm_step(eps, x, out, plan, guidance=None, mask=None, group_size=0, group_bl
         obs.after_aux(kind)
     _check(rc, "p2p_dpm_step")
     return out
+
+
+def direct_step(eps, x, out, coeffs, offset, guidance=None, mask=None, group_size=0, group_blend=None, blend=None):
+    """latent_step for Direct Inversion's edit loop (p2p_direct_step): the same arguments and, after
+    the blend, ``offset`` -- f32 [B / group_size, C, H, W], one row with group_size = 0 -- added to
+    each prompt group's first prompt.  The other prompts blend towards the un-offset source."""
+    a = DirectStepArgs()
+    sums_bytes = _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, "direct_step")
+    a.sqrt_beta_t, a.sqrt_alpha_t, a.sqrt_alpha_prev, a.sqrt_one_minus_alpha_prev = [float(c) for c in coeffs]
+    _require_cuda(offset)
+    B = x.shape[0]
+    groups = B // group_size if group_size > 0 else 1
+    if offset.dtype != torch.float32 or not offset.is_contiguous() or tuple(offset.shape) != (groups, *x.shape[1:]):
+        raise HipError(f"direct_step: offset must be contiguous f32 {(groups, *x.shape[1:])}, got "
+                       f"{offset.dtype} {tuple(offset.shape)}")
+    a.offset = offset.data_ptr()
+    kind = "direct_blend" if sums_bytes else "direct_step"
+    obs = LAUNCH_OBSERVER
+    if obs is not None and hasattr(obs, "before_aux"):
+        obs.before_aux(kind, eps.numel() * eps.element_size() + 2 * x.numel() * 4 + offset.numel() * 4 +
+                       (mask.numel() if mask is not None else 0) + sums_bytes)
+    rc = lib().p2p_direct_step(ctypes.byref(a), _stream(x.device))
+    if obs is not None and hasattr(obs, "after_aux"):
+        obs.after_aux(kind)
+    _check(rc, "p2p_direct_step")
+    return out
+
+
+def direct_offset(eps, x, target, coef, guidance: float, offset):
+    """p2p_direct_offset for R rows: eps [2R, ...] (f32 / bf16 / f16, uncond block first), x / target /
+    offset f32 [R, ...] of eps's row shape, coef f32 [R, 4] on the device (each row's prev_coeffs).
+    offset[r] = target[r] - prev_step(guided eps[r], x[r]).  Launches on the current stream."""
+    _require_cuda(eps, x, target, coef, offset)
+    R = x.shape[0]
+    n = x.numel() // max(R, 1)
+    _dense("direct_offset eps", eps, eps.dtype, 2 * R * n)
+    for name, t in (("x", x), ("target", target), ("offset", offset)):
+        _dense(f"direct_offset {name}", t, torch.float32, R * n)
+    _dense("direct_offset coef", coef, torch.float32, 4 * R)
+    a = DirectOffsetArgs()
+    a.eps, a.eps_dtype, a.guidance = eps.data_ptr(), _dtype_code(eps), float(guidance)
+    a.x, a.target, a.coef, a.offset = x.data_ptr(), target.data_ptr(), coef.data_ptr(), offset.data_ptr()
+    a.R, a.n = R, n
+    _check(lib().p2p_direct_offset(ctypes.byref(a), _stream(x.device)), "p2p_direct_offset")
+    return offset
 
 
 def attn_fwd_lse(q, k, v, o, heads, scale, lse):

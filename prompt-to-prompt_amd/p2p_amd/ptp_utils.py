@@ -89,13 +89,18 @@ def view_images(images, num_rows=1, offset_ratio=0.02):
 
 
 # ------------------------------------------------------------------ sampling loop
-def diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource=False, t_unet=None):
+def diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource=False, t_unet=None,
+                   latent_offset=None):
     """One CFG denoising step (ptp_utils.py:65-76).  With this library's DDIM, PNDM or DPM-Solver++
     scheduler and a controller whose step_callback is its own, the CFG combine, the scheduler's step and
     LocalBlend's latent blend run as one HIP kernel (p2p_latent_step / p2p_plms_step / p2p_dpm_step) --
     same result, bit for bit.
     ``t_unet``: the same timestep as a device tensor for the U-Net (a captured step must not copy
-    a host timestep to the device); the scheduler keeps reading the host ``t``."""
+    a host timestep to the device); the scheduler keeps reading the host ``t``.
+    ``latent_offset``: Direct Inversion's offset of this step (direct_inversion.py), [G, 4, h, w] for
+    the G prompt groups of the batch (G = 1: one source prompt), added to each group's source row
+    after step_callback -- in the same launch (p2p_direct_step) where the fused DDIM step applies,
+    by add_latent_offset otherwise (low_resource, a controller with its own step_callback)."""
     tu = t if t_unet is None else t_unet
     if low_resource:
         eps_u = model.unet(latents, tu, encoder_hidden_states=context[0])["sample"]
@@ -104,15 +109,35 @@ def diffusion_step(model, controller, latents, context, t, guidance_scale, low_r
     else:
         eps = model.unet(torch.cat([latents] * 2), tu, encoder_hidden_states=context)["sample"]
         eps_u, eps_c = eps.chunk(2)
-    fused = _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale)
+    if latent_offset is None:
+        fused = _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale)
+    else:
+        if latent_offset.dim() != 4 or latents.shape[0] % latent_offset.shape[0] or \
+                latent_offset.shape[1:] != latents.shape[1:]:
+            raise ValueError(f"latent_offset {tuple(latent_offset.shape)} for latents {tuple(latents.shape)}: "
+                             f"[groups, C, H, W] with a batch of whole groups")
+        fused = None if low_resource else _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t,
+                                                             guidance_scale, latent_offset)
     if fused is not None:
         return fused
     noise_pred = eps_u + guidance_scale * (eps_c - eps_u)
     latents = model.scheduler.step(noise_pred, t, latents)["prev_sample"]
-    return controller.step_callback(latents)
+    if latent_offset is None:
+        return controller.step_callback(latents)
+    return add_latent_offset(controller.step_callback(latents), latent_offset)
 
 
-def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale):
+def add_latent_offset(latents, latent_offset):
+    """Direct Inversion's three lines for G prompt groups: ``latent_offset`` [G, 4, h, w] added to the
+    first (source) row of each group of latents.shape[0] / G rows, the other rows as they are.  With
+    G = 1: torch.cat([latents[:1] + latent_offset, latents[1:]])."""
+    G = latent_offset.shape[0]
+    x = latents.reshape(G, latents.shape[0] // G, *latents.shape[1:])
+    off = latent_offset.to(latents.device)
+    return torch.cat([x[:, :1] + off[:, None], x[:, 1:]], dim=1).reshape(latents.shape)
+
+
+def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale, latent_offset=None):
     from .ddim import DDIMScheduler
     from .dpm import DPMSolverMultistepScheduler
     from .pndm import PNDMScheduler
@@ -121,6 +146,9 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
             and latents.dtype == torch.float32 and eps_u.dtype in (torch.float32, torch.bfloat16, torch.float16)
             and hasattr(controller, "fused_step_mask")):
         return None
+    if latent_offset is not None and not (isinstance(sched, DDIMScheduler) and latent_offset.is_cuda
+                                          and latent_offset.dtype == torch.float32):
+        return None         # (Direct Inversion is a DDIM method; other operands take the eager add)
     ok, mask_fn = controller.fused_step_mask()
     if not ok:
         return None
@@ -143,7 +171,7 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
         src, hist, hist_out = x, sched.history(plan), sched.history_slot(plan, x)
     else:
         plan, src, hist, hist_out = None, x, (), None
-    _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out)
+    _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out, latent_offset)
     if plms:
         sched.commit(plan, hist_out, x)
     elif dpm:
@@ -151,9 +179,10 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
     return out
 
 
-def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out):
+def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out, offset=None):
     """The step's mask (mask_fn's side effects included) and the one p2p_latent_step / p2p_plms_step /
-    p2p_dpm_step launch (``plan``: the PLMS or DPM-Solver++ call's plan, None for DDIM) that reads it."""
+    p2p_dpm_step launch (``plan``: the PLMS or DPM-Solver++ call's plan, None for DDIM) that reads it.
+    ``offset`` (DDIM only): Direct Inversion's [groups, C, H, W] rows, added by p2p_direct_step."""
     from . import _hip
     from . import dpm as dpm_mod
     from .controllers import FoldedBlendMask, StepMask, as_mask, group_mask_tensor
@@ -165,8 +194,12 @@ def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, pla
     mask, group_blend, blend = None, None, None
     blending = [e for e in entries if e is not None]
     kept = hist + ((hist_out,) if hist_out is not None else ())
+    if offset is not None:
+        offset = offset.contiguous()
+        kept = kept + (offset,)
     if not blending:
-        group_size = 0
+        # (the offsets alone still go to each group's first prompt)
+        group_size = 0 if offset is None or offset.shape[0] == 1 else x.shape[0] // offset.shape[0]
     elif (all(isinstance(e, FoldedBlendMask) for e in blending) and len({e.latent_entry()[1:] for e in blending}) == 1
           and _blend_launch_ok(src, out, eps, blending[0], kept)):
         # every blending group folded, one threshold set: the masks are built inside the latent-step
@@ -178,6 +211,12 @@ def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, pla
         mask = as_mask(entries[0])
     else:
         mask, group_size, group_blend = group_mask_tensor(entries, group_size, size)
+    if offset is not None:
+        if offset.shape[0] != (x.shape[0] // group_size if group_size > 0 else 1):
+            raise ValueError(f"latent_offset has {offset.shape[0]} rows for a batch of {x.shape[0]} prompts in "
+                             f"groups of {group_size or x.shape[0]}")
+        return _hip.direct_step(eps, x, out, sched.prev_coeffs(t), offset, guidance_scale, mask, group_size,
+                                group_blend, blend)
     if plan is None:
         return _hip.latent_step(eps, x, out, sched.prev_coeffs(t), guidance_scale, mask, group_size, group_blend, blend)
     launch = _hip.dpm_step if isinstance(plan, dpm_mod.StepPlan) else _hip.plms_step
@@ -284,9 +323,12 @@ def text2image_ldm(model, prompt: List[str], controller, num_inference_steps: in
 def text2image_ldm_stable(model, prompt: List[str], controller, num_inference_steps: int = 50,
                           guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None,
                           latent: Optional[torch.FloatTensor] = None, low_resource: bool = False,
-                          uncond_embeddings=None):
+                          uncond_embeddings=None, latent_offsets=None):
     """ptp_utils.py:129-172.  ``uncond_embeddings`` (per-step list or one tensor) is the
-    argument the missing null-text notebook passes for the edit after inversion.  With a VAE on
+    argument the missing null-text notebook passes for the edit after inversion.
+    ``latent_offsets`` (a tensor [steps, G, 4, h, w] or a per-step list of [G, 4, h, w]; G = 1 for
+    one source prompt) is what DirectInversion.invert returns: step i's entry is added to the source
+    row after that step (diffusion_step's ``latent_offset``).  With a VAE on
     the model (SyntheticStableDiffusion(vae=True)) the images come back as the reference returns
     them, uint8 [N, 512, 512, 3]; without one, the final latents in their place."""
     register_attention_control(model, controller)
@@ -309,7 +351,11 @@ def text2image_ldm_stable(model, prompt: List[str], controller, num_inference_st
             u = uncond_embeddings[i] if isinstance(uncond_embeddings, (list, tuple)) else uncond_embeddings
             uncond = u.expand(*text.shape)
             context = [uncond, text] if low_resource else torch.cat([uncond, text])
-        latents = diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource)
+        if latent_offsets is None:
+            latents = diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource)
+        else:
+            latents = diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource,
+                                     latent_offset=latent_offsets[i].to(model.device))
     image = latent2image(model.vae, latents) if getattr(model, "vae", None) is not None else latents
     return image, latent
 
