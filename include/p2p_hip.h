@@ -441,6 +441,73 @@ typedef struct {
 
 int p2p_direct_offset(const p2p_direct_offset_args* a, p2p_stream_t stream);
 
+/* The stochastic (eta > 0) DDIM step with a caller-supplied variance noise, for the edit loop of the
+ * edit-friendly DDPM inversion (Huberman-Spiegelglas, Kulikov, Michaeli, CVPR 2024, "An Edit
+ * Friendly DDPM Noise Space: Inversion and Manipulations"; p2p_amd/ddpm_inversion.py), additive to
+ * ABI 16:
+ *   out[b] = mu(x[b], eps[b]) + sigma * noise[g]      g the prompt group of prompt b
+ * and then the LocalBlend blend -- the order of scheduler.ddpm_step(..., variance_noise) followed by
+ * step_callback: the noise goes to EVERY prompt of the group, before the blend, so the rows b != g0
+ * blend towards the noised out[g0] (p2p_direct_step adds its offset to g0 alone, after the blend).
+ * mu is p2p_latent_step's update with sqrt_one_minus_alpha_prev carrying
+ * sqrt(1 - a_prev - sigma^2) (DDIMScheduler.ddpm_coeffs); sigma * noise is one f32 product, then one
+ * f32 sum, nothing contracted.  Every field of p2p_latent_step_args means what it means there, in
+ * all three forms (no mask, `mask` with groups, blend_sums), with the same preconditions; noise is
+ * f32 [n_prompts / group_size, C, H, W], one row with group_size = 0.  out is bit-identical to the
+ * eager lines; with sigma = 0 (legal: the last step of the grid) and a finite noise, to
+ * p2p_latent_step with the same four factors.
+ * Rejected with P2P_E_ARG before any launch: a NULL noise, a noise that overlaps x or out, a
+ * negative or non-finite sigma, and what p2p_direct_step rejects (in the blend_sums form a
+ * misaligned pointer, noise included); P2P_E_DTYPE: an unknown eps_dtype. */
+typedef struct {
+  const void* eps;
+  int32_t eps_dtype;               /* P2P_DTYPE_*                                      */
+  int32_t cfg;
+  float guidance;
+  const float* x;
+  float* out;                      /* may alias x (not in the blend_sums form)         */
+  int32_t n_prompts, channels, height, width;
+  float sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev;
+  float sqrt_one_minus_alpha_prev; /* sqrt(1 - a_prev - sigma^2)                       */
+  const uint8_t* mask;
+  int32_t group_size;
+  const uint8_t* group_blend;
+  const float* blend_sums[P2P_MAX_GROUPS];
+  int32_t blend_lh;
+  int32_t blend_res;
+  float blend_th_pool, blend_th_sub;
+  int32_t blend_sub;
+  float sigma;                     /* >= 0, finite                                     */
+  const float* noise;              /* f32 [n_prompts / group_size, C, H, W]            */
+} p2p_ddpm_step_args;
+
+int p2p_ddpm_step(const p2p_ddpm_step_args* a, p2p_stream_t stream);
+
+/* The noise maps of the edit-friendly DDPM inversion for R rows in one launch -- R timesteps of one
+ * image, or of several:
+ *   mu[r]    = c2 * ((x[r] - c0 * e[r]) / c1) + c3' * e[r]    e = eps_u[r] + guidance * (eps_c[r] - eps_u[r])
+ *   noise[r] = c4 > 0 ? (target[r] - mu[r]) / c4 : 0          (one IEEE division)
+ * eps [2R, n] in eps_dtype (uncond block first), x / target / noise f32 [R, n] (n = C * H * W),
+ * coef f32 [R, 5] in DEVICE memory: row r's own c0 = sqrt(1 - a_t), c1 = sqrt(a_t),
+ * c2 = sqrt(a_prev), c3' = sqrt(1 - a_prev - sigma^2), c4 = sigma (DDIMScheduler.ddpm_coeffs), since
+ * the rows are different timesteps and a graph captured once is refilled per call.  mu[r] is
+ * bit-identical to p2p_ddpm_step without a mask on row r with sigma = 0 and that row's c0 .. c3'.
+ * Rejections as p2p_direct_offset's: a null pointer, R <= 0 or n <= 0 (P2P_E_ARG); an unknown
+ * eps_dtype (P2P_E_DTYPE); R > 65535 (P2P_E_BATCH); n % 4 != 0, or eps / x / target / coef / noise
+ * off 16 bytes (P2P_E_ALIGN; coef's rows of five are read as scalars, only its base is checked). */
+typedef struct {
+  const void* eps;        /* [2R, n] in eps_dtype                                       */
+  int32_t eps_dtype;      /* P2P_DTYPE_F32 / P2P_DTYPE_BF16 / P2P_DTYPE_F16             */
+  float guidance;
+  const float* x;         /* [R, n] the noisy latent at each row's timestep             */
+  const float* target;    /* [R, n] the next cleaner level                              */
+  const float* coef;      /* [R, 5] f32, device                                         */
+  float* noise;           /* [R, n] out                                                 */
+  int32_t R, n;
+} p2p_ddpm_noise_args;
+
+int p2p_ddpm_noise(const p2p_ddpm_noise_args* a, p2p_stream_t stream);
+
 /* AttentionStore.get_average_attention (main.py:144-149): dst = src / divisor, computed as
  * src * (1.0f / divisor) -- what torch does for `cuda_tensor / python_scalar` on the
  * reference's cuda:0 device. */

@@ -312,7 +312,7 @@ __device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, 
 struct DdimC {
   int cfg;
   float guidance, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev;
-  template <typename A>   // p2p_latent_step_args, or p2p_direct_step_args (the same fields)
+  template <typename A>   // p2p_latent_step_args, p2p_direct_step_args or p2p_ddpm_step_args (the same fields)
   __device__ explicit DdimC(const A& a)
       : cfg(a.cfg), guidance(a.guidance), sqrt_beta_t(a.sqrt_beta_t), sqrt_alpha_t(a.sqrt_alpha_t),
         sqrt_alpha_prev(a.sqrt_alpha_prev), sqrt_one_minus_alpha_prev(a.sqrt_one_minus_alpha_prev) {}
@@ -437,9 +437,19 @@ struct DirectC : DdimC {
   __device__ explicit DirectC(const p2p_direct_step_args& a) : DdimC(a), offset(a.offset) {}
 };
 
+// The stochastic DDIM step of the DDPM-inversion edit loop (include/p2p_hip.h p2p_ddpm_step): the
+// DDIM step with sqrt(1 - a_prev - sigma^2) as its direction factor, then sigma times the group's
+// noise row added to every prompt of the group, before the blend
+struct DdpmC : DdimC {
+  float sigma;
+  const float* noise;
+  __device__ explicit DdpmC(const p2p_ddpm_step_args& a) : DdimC(a), sigma(a.sigma), noise(a.noise) {}
+};
+
 template <typename A> struct StepOf;
 template <> struct StepOf<p2p_latent_step_args> { using C = DdimC; };
 template <> struct StepOf<p2p_direct_step_args> { using C = DirectC; };
+template <> struct StepOf<p2p_ddpm_step_args> { using C = DdpmC; };
 template <> struct StepOf<p2p_plms_step_args> { using C = PlmsC; };
 template <> struct StepOf<p2p_dpm_step_args> { using C = DpmC; };
 
@@ -494,12 +504,28 @@ __device__ __forceinline__ float step_prev(const p2p_direct_step_args& a, int b,
   return ddim_from<DT>(a, eu, ec, a.x[(int64_t)b * chw + i]);
 }
 
+// mu + sigma z: the product rounded, then the sum (torch's two lines, never an fma)
+__device__ __forceinline__ float ddpm_noised(float mu, float sigma, float z) { return add_rn(mu, mul_rn(sigma, z)); }
+
+// the stochastic DDIM step: the noise row is the prompt group's, so prev0 -- what the group's other
+// prompts blend towards -- carries it too
+template <int DT>
+__device__ __forceinline__ float step_prev(const p2p_ddpm_step_args& a, int b, int64_t i, int64_t chw) {
+  const float eu = eps_at<DT>(a, (int64_t)b * chw + i);
+  const float ec = a.cfg ? eps_at<DT>(a, (int64_t)(a.n_prompts + b) * chw + i) : 0.f;
+  const int gs = a.group_size > 0 ? a.group_size : a.n_prompts;
+  return ddpm_noised(ddim_from<DT>(a, eu, ec, a.x[(int64_t)b * chw + i]), a.sigma, a.noise[(int64_t)(b / gs) * chw + i]);
+}
+
 template <typename A>
 constexpr bool kDirectForm = std::is_same<A, p2p_direct_step_args>::value;
+template <typename A>
+constexpr bool kDdpmForm = std::is_same<A, p2p_ddpm_step_args>::value;
 
-// A: p2p_latent_step_args (DDIM), p2p_plms_step_args, p2p_dpm_step_args or p2p_direct_step_args --
-// the step form is step_prev's overload.  The Direct Inversion form adds offset[g] to group g's
-// source prompt as it is stored: prev0, which the group's other prompts blend towards, stays un-offset.
+// A: p2p_latent_step_args (DDIM), p2p_plms_step_args, p2p_dpm_step_args, p2p_direct_step_args or
+// p2p_ddpm_step_args -- the step form is step_prev's overload.  The Direct Inversion form adds offset[g]
+// to group g's source prompt as it is stored: prev0, which the group's other prompts blend towards,
+// stays un-offset.  (The DDPM form's noise is part of its step_prev: it is in prev0 as well.)
 // (This body and latent_blend_kernel's stay in the kernels: moved into an inlined device function,
 // hipcc no longer folds the block size with the launch bounds and schedules the DDIM instantiations
 // differently; templated on the argument struct their ISA is the one-form kernels'.)
@@ -542,7 +568,9 @@ __global__ __launch_bounds__(256) void latent_step_kernel(A a, int64_t chw) {
 // DPM-Solver++ form (A = p2p_dpm_step_args) adds one history load and one store of the new x0; the
 // Direct Inversion form (A = p2p_direct_step_args) one load of the group's offset row, which the
 // source prompt's workgroups add to what they store (the edit workgroups recompute the un-offset
-// source from the inputs, as before).
+// source from the inputs, as before); the DDPM form (A = p2p_ddpm_step_args) one load of the group's
+// noise row, which every workgroup of the group adds, times sigma, to its prompt's and to the
+// recomputed source's step before it blends.
 template <int DT, typename A>
 __global__ __launch_bounds__(256, 1) void latent_blend_kernel(A a, int64_t chw, int px_per_wg) {
   // every field this kernel reads, copied to scalars first (see DdimC)
@@ -598,6 +626,7 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(A a, int64_t chw, 
     }
     f32x4_t offv = {0.f, 0.f, 0.f, 0.f};
     if constexpr (kDirectForm<A>) offv = *reinterpret_cast<const f32x4_t*>(dc.offset + (int64_t)g * chw + i);
+    if constexpr (kDdpmForm<A>) offv = *reinterpret_cast<const f32x4_t*>(dc.noise + (int64_t)g * chw + i);
     if (blend && c0 == 0) {
       const int R2 = res * res;
       build_blend_mask(ws, ws + (int64_t)bg * 2 * lh * R2, lh, res, H, W, th_pool, th_sub, use_sub != 0, L);
@@ -609,10 +638,12 @@ __global__ __launch_bounds__(256, 1) void latent_blend_kernel(A a, int64_t chw, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float prev = dc.template from<DT>(eu[j], ec[j], xv[0][j], ex[0], j, e_new[j]);
+      if constexpr (kDdpmForm<A>) prev = ddpm_noised(prev, dc.sigma, offv[j]);
       if (blend) {
         const f32x4_t eu0 = unpack(reu[1]), ec0 = unpack(rec[1]);
         float e0;
-        const float prev0 = dc.template from<DT>(eu0[j], ec0[j], xv[1][j], ex[1], j, e0);
+        float prev0 = dc.template from<DT>(eu0[j], ec0[j], xv[1][j], ex[1], j, e0);
+        if constexpr (kDdpmForm<A>) prev0 = ddpm_noised(prev0, dc.sigma, offv[j]);
         const float m = L.msrc[blend_src_of(px + j, res, H, W)];
         prev = add_rn(prev0, mul_rn(m, sub_rn(prev, prev0)));
       }
@@ -736,6 +767,20 @@ int run_direct_step(const p2p_direct_step_args& a, hipStream_t st) {
   return launch_latent_form(a, fused, st);
 }
 
+int run_ddpm_step(const p2p_ddpm_step_args& a, hipStream_t st) {
+  bool fused = false;
+  if (!a.noise || !(a.sigma >= 0.f) || __builtin_isinf(a.sigma)) return P2P_E_ARG;   // (NaN fails the comparison)
+  if (const int rc = check_latent_args(a, fused)) return rc;
+  const int gs = a.group_size > 0 ? a.group_size : a.n_prompts;
+  const int64_t chw = (int64_t)a.channels * a.height * a.width;
+  const uintptr_t nz0 = (uintptr_t)a.noise, nz1 = nz0 + (uintptr_t)(a.n_prompts / gs) * chw * 4;
+  const uintptr_t lat_bytes = (uintptr_t)a.n_prompts * chw * 4;
+  for (const uintptr_t p : {(uintptr_t)a.x, (uintptr_t)a.out})
+    if (nz0 < p + lat_bytes && p < nz1) return P2P_E_ARG;
+  if (fused && nz0 % 16) return P2P_E_ARG;
+  return launch_latent_form(a, fused, st);
+}
+
 // ---------------------------------------------------------------- Direct Inversion offsets
 // offset[r] = target[r] - prev_step(cfg(eps_u[r], eps_c[r]), x[r]) for R rows, each with its own
 // DDIM coefficients read from device memory (include/p2p_hip.h p2p_direct_offset): grid (chunks of
@@ -793,6 +838,61 @@ int run_direct_offset(const p2p_direct_offset_args& a, hipStream_t st) {
     launch_kernel(direct_offset_kernel<P2P_DTYPE_F16>, grid, dim3(256), 0, st, a);
   else
     launch_kernel(direct_offset_kernel<P2P_DTYPE_F32>, grid, dim3(256), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- DDPM inversion noise maps
+// noise[r] = (target[r] - mu[r]) / sigma[r] for R rows, each with its own five coefficients read from
+// device memory (include/p2p_hip.h p2p_ddpm_noise); direct_offset_kernel's geometry.  mu is the
+// latent step's ddim_from with c3' as its direction factor, so a row's mu is p2p_ddpm_step's at
+// sigma = 0 bit for bit; a row with sigma = 0 (the grid's last step) stores zeros.
+template <int DT>
+__global__ __launch_bounds__(256) void ddpm_noise_kernel(p2p_ddpm_noise_args a) {
+  const int r = blockIdx.y;
+  const int iv = blockIdx.x * 256 + threadIdx.x;      // 4-element piece of row r
+  if (iv >= a.n / 4) return;
+  const float* cr = a.coef + (int64_t)r * 5;
+  const OffsetC c{1, a.guidance, cr[0], cr[1], cr[2], cr[3]};
+  const float sigma = cr[4];
+  const int64_t i = (int64_t)r * a.n + (int64_t)iv * 4;
+  const int64_t ic = (int64_t)(a.R + r) * a.n + (int64_t)iv * 4;
+  f32x4_t eu, ec;
+  if constexpr (DT == P2P_DTYPE_F32) {
+    eu = *reinterpret_cast<const f32x4_t*>(static_cast<const float*>(a.eps) + i);
+    ec = *reinterpret_cast<const f32x4_t*>(static_cast<const float*>(a.eps) + ic);
+  } else {
+    const uint2 ru = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(a.eps) + i);
+    const uint2 rc = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(a.eps) + ic);
+    auto widen = [](uint32_t v) { return DT == P2P_DTYPE_BF16 ? bf2f((uint16_t)v) : h2f((uint16_t)v); };
+    eu = f32x4_t{widen(ru.x & 0xffffu), widen(ru.x >> 16), widen(ru.y & 0xffffu), widen(ru.y >> 16)};
+    ec = f32x4_t{widen(rc.x & 0xffffu), widen(rc.x >> 16), widen(rc.y & 0xffffu), widen(rc.y >> 16)};
+  }
+  const f32x4_t xv = *reinterpret_cast<const f32x4_t*>(a.x + i);
+  const f32x4_t tv = *reinterpret_cast<const f32x4_t*>(a.target + i);
+  f32x4_t o = {0.f, 0.f, 0.f, 0.f};
+  if (sigma > 0.f) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = __fdiv_rn(sub_rn(tv[j], ddim_from<DT>(c, eu[j], ec[j], xv[j])), sigma);
+  }
+  *reinterpret_cast<f32x4_t*>(a.noise + i) = o;
+}
+
+int run_ddpm_noise(const p2p_ddpm_noise_args& a, hipStream_t st) {
+  if (!a.eps || !a.x || !a.target || !a.coef || !a.noise) return P2P_E_ARG;
+  if (a.R <= 0 || a.n <= 0) return P2P_E_ARG;
+  if (a.eps_dtype != P2P_DTYPE_F32 && a.eps_dtype != P2P_DTYPE_BF16 && a.eps_dtype != P2P_DTYPE_F16)
+    return P2P_E_DTYPE;
+  if (a.R > kOffsetMaxRows) return P2P_E_BATCH;
+  if (a.n % 4) return P2P_E_ALIGN;
+  if (((uintptr_t)a.eps | (uintptr_t)a.x | (uintptr_t)a.target | (uintptr_t)a.coef | (uintptr_t)a.noise) & 15)
+    return P2P_E_ALIGN;
+  const dim3 grid((unsigned)((a.n / 4 + 255) / 256), (unsigned)a.R);
+  if (a.eps_dtype == P2P_DTYPE_BF16)
+    launch_kernel(ddpm_noise_kernel<P2P_DTYPE_BF16>, grid, dim3(256), 0, st, a);
+  else if (a.eps_dtype == P2P_DTYPE_F16)
+    launch_kernel(ddpm_noise_kernel<P2P_DTYPE_F16>, grid, dim3(256), 0, st, a);
+  else
+    launch_kernel(ddpm_noise_kernel<P2P_DTYPE_F32>, grid, dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
 

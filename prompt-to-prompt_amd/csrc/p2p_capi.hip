@@ -436,6 +436,16 @@ int p2p_direct_offset(const p2p_direct_offset_args* a, p2p_stream_t stream) {
   return run_direct_offset(*a, (hipStream_t)stream);
 }
 
+int p2p_ddpm_step(const p2p_ddpm_step_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_ddpm_step(*a, (hipStream_t)stream);
+}
+
+int p2p_ddpm_noise(const p2p_ddpm_noise_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_ddpm_noise(*a, (hipStream_t)stream);
+}
+
 int p2p_store_scale(const float* src, float* dst, float divisor, int64_t n, p2p_stream_t stream) {
   if (!src || !dst) return P2P_E_ARG;
   return run_store_scale(src, dst, divisor, n, (hipStream_t)stream);

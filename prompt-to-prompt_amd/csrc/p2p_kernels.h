@@ -132,6 +132,8 @@ int run_plms_step(const p2p_plms_step_args& a, hipStream_t st);
 int run_dpm_step(const p2p_dpm_step_args& a, hipStream_t st);
 int run_direct_step(const p2p_direct_step_args& a, hipStream_t st);
 int run_direct_offset(const p2p_direct_offset_args& a, hipStream_t st);
+int run_ddpm_step(const p2p_ddpm_step_args& a, hipStream_t st);
+int run_ddpm_noise(const p2p_ddpm_noise_args& a, hipStream_t st);
 
 // attention backward (p2p_bwd.hip)
 struct BwdArgs {

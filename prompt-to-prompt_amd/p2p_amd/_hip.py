@@ -137,6 +137,18 @@ class DirectOffsetArgs(ctypes.Structure):
     ]
 
 
+class DdpmStepArgs(ctypes.Structure):
+    _fields_ = LatentArgs._fields_ + [("sigma", ctypes.c_float), ("noise", ctypes.c_void_p)]
+
+
+class DdpmNoiseArgs(ctypes.Structure):
+    _fields_ = [
+        ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("guidance", ctypes.c_float),
+        ("x", ctypes.c_void_p), ("target", ctypes.c_void_p), ("coef", ctypes.c_void_p), ("noise", ctypes.c_void_p),
+        ("R", ctypes.c_int32), ("n", ctypes.c_int32),
+    ]
+
+
 class GroupNormArgs(ctypes.Structure):
     _fields_ = [
         ("x", ctypes.c_void_p), ("chan_add", ctypes.c_void_p), ("chan_add_stride", ctypes.c_int64),
@@ -324,6 +336,8 @@ def lib():
         L.p2p_dpm_step.argtypes = [ctypes.POINTER(DpmArgs), vp]
         L.p2p_direct_step.argtypes = [ctypes.POINTER(DirectStepArgs), vp]
         L.p2p_direct_offset.argtypes = [ctypes.POINTER(DirectOffsetArgs), vp]
+        L.p2p_ddpm_step.argtypes = [ctypes.POINTER(DdpmStepArgs), vp]
+        L.p2p_ddpm_noise.argtypes = [ctypes.POINTER(DdpmNoiseArgs), vp]
         L.p2p_attn_fwd_lse.argtypes = [ctypes.POINTER(AttnTensors), vp, vp]
         L.p2p_attn_bwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
         L.p2p_attn_bwd_workspace.argtypes = [ctypes.POINTER(AttnTensors)]
@@ -385,7 +399,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_map_panels", "p2p_null_loss", "p2p_null_adam", "p2p_group_norm_bwd",
                     "p2p_group_norm_bwd_workspace_floats", "p2p_geglu_bwd", "p2p_nchw_to_tokens", "p2p_time_embed",
                     "p2p_time_proj", "p2p_conv3x3", "p2p_conv3x3_split", "p2p_conv3x3_workspace_floats",
-                    "p2p_conv3x3_pack", "p2p_dpm_step", "p2p_direct_step", "p2p_direct_offset")
+                    "p2p_conv3x3_pack", "p2p_dpm_step", "p2p_direct_step", "p2p_direct_offset",
+                    "p2p_ddpm_step", "p2p_ddpm_noise")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -834,6 +849,61 @@ def direct_offset(eps, x, target, coef, guidance: float, offset):
     a.R, a.n = R, n
     _check(lib().p2p_direct_offset(ctypes.byref(a), _stream(x.device)), "p2p_direct_offset")
     return offset
+
+
+def ddpm_step(eps, x, out, coeffs, noise, guidance=None, mask=None, group_size=0, group_blend=None, blend=None):
+    """latent_step with a variance noise, for the DDPM-inversion edit loop (p2p_ddpm_step): the same
+    arguments with ``coeffs`` the five of DDIMScheduler.ddpm_coeffs -- (sqrt(1 - a_t), sqrt(a_t),
+    sqrt(a_prev), sqrt(1 - a_prev - sigma^2), sigma) -- and ``noise`` f32 [B / group_size, C, H, W],
+    one row with group_size = 0: sigma * noise[g] is added to every prompt of group g before the
+    blend."""
+    a = DdpmStepArgs()
+    sums_bytes = _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, "ddpm_step")
+    (a.sqrt_beta_t, a.sqrt_alpha_t, a.sqrt_alpha_prev, a.sqrt_one_minus_alpha_prev,
+     a.sigma) = [float(c) for c in coeffs]
+    _require_cuda(noise)
+    B = x.shape[0]
+    groups = B // group_size if group_size > 0 else 1
+    if noise.dtype != torch.float32 or not noise.is_contiguous() or tuple(noise.shape) != (groups, *x.shape[1:]):
+        raise HipError(f"ddpm_step: noise must be contiguous f32 {(groups, *x.shape[1:])}, got "
+                       f"{noise.dtype} {tuple(noise.shape)}")
+    a.noise = noise.data_ptr()
+    kind = "ddpm_blend" if sums_bytes else "ddpm_step"
+    obs = LAUNCH_OBSERVER
+    if obs is not None and hasattr(obs, "before_aux"):
+        obs.before_aux(kind, eps.numel() * eps.element_size() + 2 * x.numel() * 4 + noise.numel() * 4 +
+                       (mask.numel() if mask is not None else 0) + sums_bytes)
+    rc = lib().p2p_ddpm_step(ctypes.byref(a), _stream(x.device))
+    if obs is not None and hasattr(obs, "after_aux"):
+        obs.after_aux(kind)
+    _check(rc, "p2p_ddpm_step")
+    return out
+
+
+def ddpm_noise(eps, x, target, coef, guidance: float, noise):
+    """p2p_ddpm_noise for R rows: eps [2R, ...] (f32 / bf16 / f16, uncond block first), x / target /
+    noise f32 [R, ...] of eps's row shape, coef f32 [R, 5] on the device (each row's ddpm_coeffs).
+    noise[r] = (target[r] - mu(guided eps[r], x[r])) / sigma[r], zeros where sigma[r] is 0.  Launches
+    on the current stream."""
+    _require_cuda(eps, x, target, coef, noise)
+    R = x.shape[0]
+    n = x.numel() // max(R, 1)
+    _dense("ddpm_noise eps", eps, eps.dtype, 2 * R * n)
+    for name, t in (("x", x), ("target", target), ("noise", noise)):
+        _dense(f"ddpm_noise {name}", t, torch.float32, R * n)
+    _dense("ddpm_noise coef", coef, torch.float32, 5 * R)
+    a = DdpmNoiseArgs()
+    a.eps, a.eps_dtype, a.guidance = eps.data_ptr(), _dtype_code(eps), float(guidance)
+    a.x, a.target, a.coef, a.noise = x.data_ptr(), target.data_ptr(), coef.data_ptr(), noise.data_ptr()
+    a.R, a.n = R, n
+    obs = LAUNCH_OBSERVER
+    if obs is not None and hasattr(obs, "before_aux"):
+        obs.before_aux("ddpm_noise", eps.numel() * eps.element_size() + 3 * x.numel() * 4 + coef.numel() * 4)
+    rc = lib().p2p_ddpm_noise(ctypes.byref(a), _stream(x.device))
+    if obs is not None and hasattr(obs, "after_aux"):
+        obs.after_aux("ddpm_noise")
+    _check(rc, "p2p_ddpm_noise")
+    return noise
 
 
 def attn_fwd_lse(q, k, v, o, heads, scale, lse):

@@ -90,7 +90,7 @@ def view_images(images, num_rows=1, offset_ratio=0.02):
 
 # ------------------------------------------------------------------ sampling loop
 def diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource=False, t_unet=None,
-                   latent_offset=None):
+                   latent_offset=None, latent_noise=None, eta=1.0):
     """One CFG denoising step (ptp_utils.py:65-76).  With this library's DDIM, PNDM or DPM-Solver++
     scheduler and a controller whose step_callback is its own, the CFG combine, the scheduler's step and
     LocalBlend's latent blend run as one HIP kernel (p2p_latent_step / p2p_plms_step / p2p_dpm_step) --
@@ -100,7 +100,25 @@ def diffusion_step(model, controller, latents, context, t, guidance_scale, low_r
     ``latent_offset``: Direct Inversion's offset of this step (direct_inversion.py), [G, 4, h, w] for
     the G prompt groups of the batch (G = 1: one source prompt), added to each group's source row
     after step_callback -- in the same launch (p2p_direct_step) where the fused DDIM step applies,
-    by add_latent_offset otherwise (low_resource, a controller with its own step_callback)."""
+    by add_latent_offset otherwise (low_resource, a controller with its own step_callback).
+    ``latent_noise``: the DDPM inversion's noise map of this step (ddpm_inversion.py), [G, 4, h, w]:
+    the step becomes the stochastic one at ``eta`` (DDIMScheduler.ddpm_step) with group g's map as the
+    variance noise of every row of the group, added BEFORE step_callback -- in the same launch
+    (p2p_ddpm_step) where the fused DDIM step applies, by scheduler.ddpm_step otherwise.  DDIM
+    only; not together with ``latent_offset``."""
+    if latent_noise is not None:
+        if latent_offset is not None:
+            raise ValueError("latent_noise (DDPM inversion) and latent_offset (Direct Inversion) are two methods: "
+                             "pass one of them")
+        if not (float(eta) > 0):
+            raise ValueError(f"eta must be positive with latent_noise, got {eta}")
+        if not hasattr(model.scheduler, "ddpm_step"):
+            raise TypeError(f"latent_noise needs the DDIM scheduler: {type(model.scheduler).__name__} has no "
+                            f"prev_step / ddpm_step (build the model with scheduler='ddim')")
+        if latent_noise.dim() != 4 or latents.shape[0] % latent_noise.shape[0] or \
+                latent_noise.shape[1:] != latents.shape[1:]:
+            raise ValueError(f"latent_noise {tuple(latent_noise.shape)} for latents {tuple(latents.shape)}: "
+                             f"[groups, C, H, W] with a batch of whole groups")
     tu = t if t_unet is None else t_unet
     if low_resource:
         eps_u = model.unet(latents, tu, encoder_hidden_states=context[0])["sample"]
@@ -109,6 +127,15 @@ def diffusion_step(model, controller, latents, context, t, guidance_scale, low_r
     else:
         eps = model.unet(torch.cat([latents] * 2), tu, encoder_hidden_states=context)["sample"]
         eps_u, eps_c = eps.chunk(2)
+    if latent_noise is not None:
+        fused = None if low_resource else _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t,
+                                                             guidance_scale, None, latent_noise, eta)
+        if fused is not None:
+            return fused
+        noise_pred = eps_u + guidance_scale * (eps_c - eps_u)
+        G = latent_noise.shape[0]
+        z = latent_noise.to(latents.device).repeat_interleave(latents.shape[0] // G, 0)
+        return controller.step_callback(model.scheduler.ddpm_step(noise_pred, t, latents, z, eta))
     if latent_offset is None:
         fused = _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale)
     else:
@@ -137,7 +164,8 @@ def add_latent_offset(latents, latent_offset):
     return torch.cat([x[:, :1] + off[:, None], x[:, 1:]], dim=1).reshape(latents.shape)
 
 
-def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale, latent_offset=None):
+def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidance_scale, latent_offset=None,
+                       latent_noise=None, eta=1.0):
     from .ddim import DDIMScheduler
     from .dpm import DPMSolverMultistepScheduler
     from .pndm import PNDMScheduler
@@ -149,6 +177,9 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
     if latent_offset is not None and not (isinstance(sched, DDIMScheduler) and latent_offset.is_cuda
                                           and latent_offset.dtype == torch.float32):
         return None         # (Direct Inversion is a DDIM method; other operands take the eager add)
+    if latent_noise is not None and not (isinstance(sched, DDIMScheduler) and latent_noise.is_cuda
+                                         and latent_noise.dtype == torch.float32):
+        return None         # (a scheduler object of the caller's own, other operands: scheduler.ddpm_step)
     ok, mask_fn = controller.fused_step_mask()
     if not ok:
         return None
@@ -171,7 +202,8 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
         src, hist, hist_out = x, sched.history(plan), sched.history_slot(plan, x)
     else:
         plan, src, hist, hist_out = None, x, (), None
-    _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out, latent_offset)
+    _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out, latent_offset,
+                        latent_noise, eta)
     if plms:
         sched.commit(plan, hist_out, x)
     elif dpm:
@@ -179,10 +211,12 @@ def _fused_latent_step(model, controller, eps, eps_u, eps_c, latents, t, guidanc
     return out
 
 
-def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out, offset=None):
+def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, plan, hist, hist_out, offset=None,
+                        noise=None, eta=1.0):
     """The step's mask (mask_fn's side effects included) and the one p2p_latent_step / p2p_plms_step /
     p2p_dpm_step launch (``plan``: the PLMS or DPM-Solver++ call's plan, None for DDIM) that reads it.
-    ``offset`` (DDIM only): Direct Inversion's [groups, C, H, W] rows, added by p2p_direct_step."""
+    ``offset`` (DDIM only): Direct Inversion's [groups, C, H, W] rows, added by p2p_direct_step;
+    ``noise`` (DDIM only, instead of it): the DDPM inversion's rows, added by p2p_ddpm_step at ``eta``."""
     from . import _hip
     from . import dpm as dpm_mod
     from .controllers import FoldedBlendMask, StepMask, as_mask, group_mask_tensor
@@ -194,12 +228,13 @@ def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, pla
     mask, group_blend, blend = None, None, None
     blending = [e for e in entries if e is not None]
     kept = hist + ((hist_out,) if hist_out is not None else ())
-    if offset is not None:
-        offset = offset.contiguous()
-        kept = kept + (offset,)
+    rows = offset if offset is not None else noise     # the per-group operand of the step, if any
+    if rows is not None:
+        rows = rows.contiguous()
+        kept = kept + (rows,)
     if not blending:
-        # (the offsets alone still go to each group's first prompt)
-        group_size = 0 if offset is None or offset.shape[0] == 1 else x.shape[0] // offset.shape[0]
+        # (the offsets alone still go to each group's first prompt, the noise to each group's rows)
+        group_size = 0 if rows is None or rows.shape[0] == 1 else x.shape[0] // rows.shape[0]
     elif (all(isinstance(e, FoldedBlendMask) for e in blending) and len({e.latent_entry()[1:] for e in blending}) == 1
           and _blend_launch_ok(src, out, eps, blending[0], kept)):
         # every blending group folded, one threshold set: the masks are built inside the latent-step
@@ -211,11 +246,14 @@ def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, pla
         mask = as_mask(entries[0])
     else:
         mask, group_size, group_blend = group_mask_tensor(entries, group_size, size)
-    if offset is not None:
-        if offset.shape[0] != (x.shape[0] // group_size if group_size > 0 else 1):
-            raise ValueError(f"latent_offset has {offset.shape[0]} rows for a batch of {x.shape[0]} prompts in "
-                             f"groups of {group_size or x.shape[0]}")
-        return _hip.direct_step(eps, x, out, sched.prev_coeffs(t), offset, guidance_scale, mask, group_size,
+    if rows is not None:
+        if rows.shape[0] != (x.shape[0] // group_size if group_size > 0 else 1):
+            raise ValueError(f"{'latent_offset' if offset is not None else 'latent_noise'} has {rows.shape[0]} rows "
+                             f"for a batch of {x.shape[0]} prompts in groups of {group_size or x.shape[0]}")
+        if offset is None:
+            return _hip.ddpm_step(eps, x, out, sched.ddpm_coeffs(t, eta), rows, guidance_scale, mask, group_size,
+                                  group_blend, blend)
+        return _hip.direct_step(eps, x, out, sched.prev_coeffs(t), rows, guidance_scale, mask, group_size,
                                 group_blend, blend)
     if plan is None:
         return _hip.latent_step(eps, x, out, sched.prev_coeffs(t), guidance_scale, mask, group_size, group_blend, blend)
@@ -323,12 +361,19 @@ def text2image_ldm(model, prompt: List[str], controller, num_inference_steps: in
 def text2image_ldm_stable(model, prompt: List[str], controller, num_inference_steps: int = 50,
                           guidance_scale: float = 7.5, generator: Optional[torch.Generator] = None,
                           latent: Optional[torch.FloatTensor] = None, low_resource: bool = False,
-                          uncond_embeddings=None, latent_offsets=None):
+                          uncond_embeddings=None, latent_offsets=None, latent_noise=None, eta: float = 1.0,
+                          first_step: int = 0):
     """ptp_utils.py:129-172.  ``uncond_embeddings`` (per-step list or one tensor) is the
     argument the missing null-text notebook passes for the edit after inversion.
     ``latent_offsets`` (a tensor [steps, G, 4, h, w] or a per-step list of [G, 4, h, w]; G = 1 for
     one source prompt) is what DirectInversion.invert returns: step i's entry is added to the source
-    row after that step (diffusion_step's ``latent_offset``).  With a VAE on
+    row after that step (diffusion_step's ``latent_offset``).
+    ``latent_noise`` (a tensor [steps, G, 4, h, w] or a per-step list of [G, 4, h, w]) is what
+    DDPMInversion.invert returns: step i runs the stochastic step at ``eta`` with entry i as the
+    variance noise of every row of its group (diffusion_step's ``latent_noise``).  ``first_step``: the
+    loop runs timesteps[first_step:] (``latent`` is then the level the inversion returned for that
+    ``skip``); latent_noise / latent_offsets / uncond_embeddings stay indexed by the absolute step,
+    and the controller is the caller's, built for num_inference_steps - first_step steps.  With a VAE on
     the model (SyntheticStableDiffusion(vae=True)) the images come back as the reference returns
     them, uint8 [N, 512, 512, 3]; without one, the final latents in their place."""
     register_attention_control(model, controller)
@@ -346,12 +391,22 @@ def text2image_ldm_stable(model, prompt: List[str], controller, num_inference_st
     # embeddings make a new context every step
     context = None if uncond_embeddings is not None else unet_context(
         model, [uncond, text] if low_resource else torch.cat([uncond, text]))
+    if latent_noise is not None and latent_offsets is not None:
+        raise ValueError("latent_noise (DDPM inversion) and latent_offsets (Direct Inversion) are two methods: "
+                         "pass one of them")
+    if not 0 <= int(first_step) < num_inference_steps:
+        raise ValueError(f"first_step must be in 0 .. {num_inference_steps - 1}, got {first_step}")
     for i, t in enumerate(model.scheduler.timesteps):
+        if i < first_step:
+            continue
         if uncond_embeddings is not None:
             u = uncond_embeddings[i] if isinstance(uncond_embeddings, (list, tuple)) else uncond_embeddings
             uncond = u.expand(*text.shape)
             context = [uncond, text] if low_resource else torch.cat([uncond, text])
-        if latent_offsets is None:
+        if latent_noise is not None:
+            latents = diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource,
+                                     latent_noise=latent_noise[i].to(model.device), eta=eta)
+        elif latent_offsets is None:
             latents = diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource)
         else:
             latents = diffusion_step(model, controller, latents, context, t, guidance_scale, low_resource,
