@@ -82,28 +82,31 @@ class BlendArgs(ctypes.Structure):
     ]
 
 
+# The five step argument structs (include/p2p_hip.h) share their head and their LocalBlend fields; the
+# DDIM family carries its four factors between the two, the multistep forms their history after.
+_STEP_HEAD = [
+    ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("cfg", ctypes.c_int32),
+    ("guidance", ctypes.c_float), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
+    ("n_prompts", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
+    ("width", ctypes.c_int32),
+]
+_DDIM_FACTORS = [
+    ("sqrt_beta_t", ctypes.c_float), ("sqrt_alpha_t", ctypes.c_float),
+    ("sqrt_alpha_prev", ctypes.c_float), ("sqrt_one_minus_alpha_prev", ctypes.c_float),
+]
+_STEP_BLEND = [
+    ("mask", ctypes.c_void_p), ("group_size", ctypes.c_int32), ("group_blend", ctypes.c_void_p),
+    ("blend_sums", ctypes.c_void_p * MAX_GROUPS), ("blend_lh", ctypes.c_int32), ("blend_res", ctypes.c_int32),
+    ("blend_th_pool", ctypes.c_float), ("blend_th_sub", ctypes.c_float), ("blend_sub", ctypes.c_int32),
+]
+
+
 class LatentArgs(ctypes.Structure):
-    _fields_ = [
-        ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("cfg", ctypes.c_int32),
-        ("guidance", ctypes.c_float), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
-        ("n_prompts", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
-        ("width", ctypes.c_int32), ("sqrt_beta_t", ctypes.c_float), ("sqrt_alpha_t", ctypes.c_float),
-        ("sqrt_alpha_prev", ctypes.c_float), ("sqrt_one_minus_alpha_prev", ctypes.c_float),
-        ("mask", ctypes.c_void_p), ("group_size", ctypes.c_int32), ("group_blend", ctypes.c_void_p),
-        ("blend_sums", ctypes.c_void_p * MAX_GROUPS), ("blend_lh", ctypes.c_int32), ("blend_res", ctypes.c_int32),
-        ("blend_th_pool", ctypes.c_float), ("blend_th_sub", ctypes.c_float), ("blend_sub", ctypes.c_int32),
-    ]
+    _fields_ = _STEP_HEAD + _DDIM_FACTORS + _STEP_BLEND
 
 
 class PlmsArgs(ctypes.Structure):
-    _fields_ = [
-        ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("cfg", ctypes.c_int32),
-        ("guidance", ctypes.c_float), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
-        ("n_prompts", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
-        ("width", ctypes.c_int32),
-        ("mask", ctypes.c_void_p), ("group_size", ctypes.c_int32), ("group_blend", ctypes.c_void_p),
-        ("blend_sums", ctypes.c_void_p * MAX_GROUPS), ("blend_lh", ctypes.c_int32), ("blend_res", ctypes.c_int32),
-        ("blend_th_pool", ctypes.c_float), ("blend_th_sub", ctypes.c_float), ("blend_sub", ctypes.c_int32),
+    _fields_ = _STEP_HEAD + _STEP_BLEND + [
         ("hist", ctypes.c_void_p * 4), ("n_hist", ctypes.c_int32), ("w", ctypes.c_float * 5),
         ("hist_out", ctypes.c_void_p),
         ("sample_coeff", ctypes.c_float), ("eps_num", ctypes.c_float), ("eps_den", ctypes.c_float),
@@ -111,14 +114,7 @@ class PlmsArgs(ctypes.Structure):
 
 
 class DpmArgs(ctypes.Structure):
-    _fields_ = [
-        ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("cfg", ctypes.c_int32),
-        ("guidance", ctypes.c_float), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
-        ("n_prompts", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
-        ("width", ctypes.c_int32),
-        ("mask", ctypes.c_void_p), ("group_size", ctypes.c_int32), ("group_blend", ctypes.c_void_p),
-        ("blend_sums", ctypes.c_void_p * MAX_GROUPS), ("blend_lh", ctypes.c_int32), ("blend_res", ctypes.c_int32),
-        ("blend_th_pool", ctypes.c_float), ("blend_th_sub", ctypes.c_float), ("blend_sub", ctypes.c_int32),
+    _fields_ = _STEP_HEAD + _STEP_BLEND + [
         ("hist", ctypes.c_void_p * 1), ("n_hist", ctypes.c_int32), ("hist_out", ctypes.c_void_p),
         ("sigma_s", ctypes.c_float), ("alpha_s", ctypes.c_float), ("x_coeff", ctypes.c_float),
         ("m0_coeff", ctypes.c_float), ("diff_coeff", ctypes.c_float),
@@ -129,24 +125,25 @@ class DirectStepArgs(ctypes.Structure):
     _fields_ = LatentArgs._fields_ + [("offset", ctypes.c_void_p)]
 
 
-class DirectOffsetArgs(ctypes.Structure):
-    _fields_ = [
-        ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("guidance", ctypes.c_float),
-        ("x", ctypes.c_void_p), ("target", ctypes.c_void_p), ("coef", ctypes.c_void_p), ("offset", ctypes.c_void_p),
-        ("R", ctypes.c_int32), ("n", ctypes.c_int32),
-    ]
-
-
 class DdpmStepArgs(ctypes.Structure):
     _fields_ = LatentArgs._fields_ + [("sigma", ctypes.c_float), ("noise", ctypes.c_void_p)]
 
 
-class DdpmNoiseArgs(ctypes.Structure):
-    _fields_ = [
+def _row_args_fields(out_name):
+    """p2p_direct_offset_args / p2p_ddpm_noise_args: the same struct up to the name of its output."""
+    return [
         ("eps", ctypes.c_void_p), ("eps_dtype", ctypes.c_int32), ("guidance", ctypes.c_float),
-        ("x", ctypes.c_void_p), ("target", ctypes.c_void_p), ("coef", ctypes.c_void_p), ("noise", ctypes.c_void_p),
+        ("x", ctypes.c_void_p), ("target", ctypes.c_void_p), ("coef", ctypes.c_void_p), (out_name, ctypes.c_void_p),
         ("R", ctypes.c_int32), ("n", ctypes.c_int32),
     ]
+
+
+class DirectOffsetArgs(ctypes.Structure):
+    _fields_ = _row_args_fields("offset")
+
+
+class DdpmNoiseArgs(ctypes.Structure):
+    _fields_ = _row_args_fields("noise")
 
 
 class GroupNormArgs(ctypes.Structure):
@@ -663,8 +660,8 @@ def store_scale(src: torch.Tensor, divisor: float, out: Optional[torch.Tensor] =
 
 
 def _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, what):
-    """The fields the three latent-step argument structs share (a: LatentArgs, PlmsArgs or DpmArgs),
-    checked and filled; returns the bytes of folded word sums the launch reads (0: no ``blend``)."""
+    """The fields the five step argument structs share (_STEP_HEAD and _STEP_BLEND), checked and
+    filled; returns the bytes of folded word sums the launch reads (0: no ``blend``)."""
     _require_cuda(eps, x, out, mask)
     for t in (eps, x, out):
         assert t.is_contiguous()
@@ -713,6 +710,44 @@ def _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blen
     return sums_bytes
 
 
+def _launch(fn, entry, a, device, kind=None, moved=(), more_bytes=0):
+    """fn(a, the current stream) -- ``fn`` the library's ``entry`` -- checked; with ``kind`` and a
+    LAUNCH_OBSERVER, reported to it as ``kind`` with the call's algorithmic bytes: every tensor of
+    ``moved`` once per read or write (None entries skipped) plus ``more_bytes``.  One frame and no
+    byte count without an observer: the call is on the host's path between two launches."""
+    obs = LAUNCH_OBSERVER if kind is not None else None
+    if obs is not None and hasattr(obs, "before_aux"):
+        obs.before_aux(kind, sum(t.numel() * t.element_size() for t in moved if t is not None) + more_bytes)
+    rc = fn(ctypes.byref(a), _stream(device))
+    if obs is not None and hasattr(obs, "after_aux"):
+        obs.after_aux(kind)
+    _check(rc, entry)
+
+
+def _group_rows(what, name, rows, x, group_size):
+    """The data pointer of a per-group row tensor (direct_step's offset, ddpm_step's noise), checked:
+    contiguous f32 [B / group_size, C, H, W], one row with group_size = 0."""
+    _require_cuda(rows)
+    groups = x.shape[0] // group_size if group_size > 0 else 1
+    if rows.dtype != torch.float32 or not rows.is_contiguous() or tuple(rows.shape) != (groups, *x.shape[1:]):
+        raise HipError(f"{what}: {name} must be contiguous f32 {(groups, *x.shape[1:])}, got "
+                       f"{rows.dtype} {tuple(rows.shape)}")
+    return rows.data_ptr()
+
+
+def _set_history(what, a, x, hist, hist_out):
+    """The multistep forms' history fields (a: PlmsArgs or DpmArgs), checked and filled: ``hist`` the
+    stored tensors the plan reads, ``hist_out`` None or the tensor that receives this call's."""
+    _require_cuda(hist_out, *hist)
+    for h in tuple(hist) + ((hist_out,) if hist_out is not None else ()):
+        if h.dtype != torch.float32 or not h.is_contiguous() or h.shape != x.shape:
+            raise HipError(f"{what}: history tensors must be contiguous f32 of the latent's shape")
+    for i, h in enumerate(hist):
+        a.hist[i] = h.data_ptr()
+    a.n_hist = len(hist)
+    a.hist_out = hist_out.data_ptr() if hist_out is not None else None
+
+
 def latent_step(eps, x, out, coeffs, guidance=None, mask=None, group_size=0, group_blend=None, blend=None):
     """Fused CFG + DDIM step + LocalBlend blend (p2p_latent_step).  eps: [2B or B, C, H, W]
     (f32/bf16/f16, uncond block first when guidance is given); x, out: f32 [B, C, H, W] (out may be
@@ -725,16 +760,8 @@ def latent_step(eps, x, out, coeffs, guidance=None, mask=None, group_size=0, gro
     a = LatentArgs()
     sums_bytes = _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, "latent_step")
     a.sqrt_beta_t, a.sqrt_alpha_t, a.sqrt_alpha_prev, a.sqrt_one_minus_alpha_prev = [float(c) for c in coeffs]
-    obs = LAUNCH_OBSERVER
-    if obs is not None and hasattr(obs, "before_aux"):
-        # algorithmic bytes: eps read, x read, out written, mask (or the folded word sums) read
-        obs.before_aux("latent_blend" if sums_bytes else "latent_step",
-                       eps.numel() * eps.element_size() + 2 * x.numel() * 4 +
-                       (mask.numel() if mask is not None else 0) + sums_bytes)
-    rc = lib().p2p_latent_step(ctypes.byref(a), _stream(x.device))
-    if obs is not None and hasattr(obs, "after_aux"):
-        obs.after_aux("latent_blend" if sums_bytes else "latent_step")
-    _check(rc, "p2p_latent_step")
+    _launch(lib().p2p_latent_step, "p2p_latent_step", a, x.device, "latent_blend" if sums_bytes else "latent_step",
+            (eps, x, out, mask), sums_bytes)
     return out
 
 
@@ -750,26 +777,12 @@ def plms_step(eps, x, out, plan, guidance=None, mask=None, group_size=0, group_b
     n_hist = int(plan.n_hist)
     if n_hist != len(hist) or len(plan.weights) != n_hist + 1 or n_hist > 4:
         raise HipError(f"plms_step: {len(hist)} history tensors for a plan of {n_hist} (weights {len(plan.weights)})")
-    _require_cuda(hist_out, *hist)
-    for h in tuple(hist) + ((hist_out,) if hist_out is not None else ()):
-        if h.dtype != torch.float32 or not h.is_contiguous() or h.shape != x.shape:
-            raise HipError("plms_step: history tensors must be contiguous f32 of the latent's shape")
-    for i, h in enumerate(hist):
-        a.hist[i] = h.data_ptr()
-    a.n_hist = n_hist
+    _set_history("plms_step", a, x, hist, hist_out)
     for i, w in enumerate(plan.weights):
         a.w[i] = float(w)
-    a.hist_out = hist_out.data_ptr() if hist_out is not None else None
     a.sample_coeff, a.eps_num, a.eps_den = float(plan.sample_coeff), float(plan.eps_num), float(plan.eps_den)
-    kind = "plms_blend" if sums_bytes else "plms_step"
-    obs = LAUNCH_OBSERVER
-    if obs is not None and hasattr(obs, "before_aux"):
-        obs.before_aux(kind, eps.numel() * eps.element_size() + (2 + n_hist + (hist_out is not None)) * x.numel() * 4 +
-                       (mask.numel() if mask is not None else 0) + sums_bytes)
-    rc = lib().p2p_plms_step(ctypes.byref(a), _stream(x.device))
-    if obs is not None and hasattr(obs, "after_aux"):
-        obs.after_aux(kind)
-    _check(rc, "p2p_plms_step")
+    _launch(lib().p2p_plms_step, "p2p_plms_step", a, x.device, "plms_blend" if sums_bytes else "plms_step",
+            (eps, x, out, mask, *hist, hist_out), sums_bytes)
     return out
 
 
@@ -785,24 +798,11 @@ def dpm_step(eps, x, out, plan, guidance=None, mask=None, group_size=0, group_bl
     n_hist = int(plan.n_hist)
     if n_hist != len(hist) or n_hist > 1:
         raise HipError(f"dpm_step: {len(hist)} history tensors for a plan of {n_hist}")
-    _require_cuda(hist_out, *hist)
-    for h in tuple(hist) + ((hist_out,) if hist_out is not None else ()):
-        if h.dtype != torch.float32 or not h.is_contiguous() or h.shape != x.shape:
-            raise HipError("dpm_step: history tensors must be contiguous f32 of the latent's shape")
-    a.hist[0] = hist[0].data_ptr() if n_hist else None
-    a.n_hist = n_hist
-    a.hist_out = hist_out.data_ptr() if hist_out is not None else None
+    _set_history("dpm_step", a, x, hist, hist_out)
     a.sigma_s, a.alpha_s, a.x_coeff = float(plan.sigma_s), float(plan.alpha_s), float(plan.x_coeff)
     a.m0_coeff, a.diff_coeff = float(plan.m0_coeff), float(plan.diff_coeff)
-    kind = "dpm_blend" if sums_bytes else "dpm_step"
-    obs = LAUNCH_OBSERVER
-    if obs is not None and hasattr(obs, "before_aux"):
-        obs.before_aux(kind, eps.numel() * eps.element_size() + (2 + n_hist + (hist_out is not None)) * x.numel() * 4 +
-                       (mask.numel() if mask is not None else 0) + sums_bytes)
-    rc = lib().p2p_dpm_step(ctypes.byref(a), _stream(x.device))
-    if obs is not None and hasattr(obs, "after_aux"):
-        obs.after_aux(kind)
-    _check(rc, "p2p_dpm_step")
+    _launch(lib().p2p_dpm_step, "p2p_dpm_step", a, x.device, "dpm_blend" if sums_bytes else "dpm_step",
+            (eps, x, out, mask, *hist, hist_out), sums_bytes)
     return out
 
 
@@ -813,42 +813,10 @@ def direct_step(eps, x, out, coeffs, offset, guidance=None, mask=None, group_siz
     a = DirectStepArgs()
     sums_bytes = _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, "direct_step")
     a.sqrt_beta_t, a.sqrt_alpha_t, a.sqrt_alpha_prev, a.sqrt_one_minus_alpha_prev = [float(c) for c in coeffs]
-    _require_cuda(offset)
-    B = x.shape[0]
-    groups = B // group_size if group_size > 0 else 1
-    if offset.dtype != torch.float32 or not offset.is_contiguous() or tuple(offset.shape) != (groups, *x.shape[1:]):
-        raise HipError(f"direct_step: offset must be contiguous f32 {(groups, *x.shape[1:])}, got "
-                       f"{offset.dtype} {tuple(offset.shape)}")
-    a.offset = offset.data_ptr()
-    kind = "direct_blend" if sums_bytes else "direct_step"
-    obs = LAUNCH_OBSERVER
-    if obs is not None and hasattr(obs, "before_aux"):
-        obs.before_aux(kind, eps.numel() * eps.element_size() + 2 * x.numel() * 4 + offset.numel() * 4 +
-                       (mask.numel() if mask is not None else 0) + sums_bytes)
-    rc = lib().p2p_direct_step(ctypes.byref(a), _stream(x.device))
-    if obs is not None and hasattr(obs, "after_aux"):
-        obs.after_aux(kind)
-    _check(rc, "p2p_direct_step")
+    a.offset = _group_rows("direct_step", "offset", offset, x, group_size)
+    _launch(lib().p2p_direct_step, "p2p_direct_step", a, x.device, "direct_blend" if sums_bytes else "direct_step",
+            (eps, x, out, mask, offset), sums_bytes)
     return out
-
-
-def direct_offset(eps, x, target, coef, guidance: float, offset):
-    """p2p_direct_offset for R rows: eps [2R, ...] (f32 / bf16 / f16, uncond block first), x / target /
-    offset f32 [R, ...] of eps's row shape, coef f32 [R, 4] on the device (each row's prev_coeffs).
-    offset[r] = target[r] - prev_step(guided eps[r], x[r]).  Launches on the current stream."""
-    _require_cuda(eps, x, target, coef, offset)
-    R = x.shape[0]
-    n = x.numel() // max(R, 1)
-    _dense("direct_offset eps", eps, eps.dtype, 2 * R * n)
-    for name, t in (("x", x), ("target", target), ("offset", offset)):
-        _dense(f"direct_offset {name}", t, torch.float32, R * n)
-    _dense("direct_offset coef", coef, torch.float32, 4 * R)
-    a = DirectOffsetArgs()
-    a.eps, a.eps_dtype, a.guidance = eps.data_ptr(), _dtype_code(eps), float(guidance)
-    a.x, a.target, a.coef, a.offset = x.data_ptr(), target.data_ptr(), coef.data_ptr(), offset.data_ptr()
-    a.R, a.n = R, n
-    _check(lib().p2p_direct_offset(ctypes.byref(a), _stream(x.device)), "p2p_direct_offset")
-    return offset
 
 
 def ddpm_step(eps, x, out, coeffs, noise, guidance=None, mask=None, group_size=0, group_blend=None, blend=None):
@@ -861,49 +829,43 @@ def ddpm_step(eps, x, out, coeffs, noise, guidance=None, mask=None, group_size=0
     sums_bytes = _latent_common(a, eps, x, out, guidance, mask, group_size, group_blend, blend, "ddpm_step")
     (a.sqrt_beta_t, a.sqrt_alpha_t, a.sqrt_alpha_prev, a.sqrt_one_minus_alpha_prev,
      a.sigma) = [float(c) for c in coeffs]
-    _require_cuda(noise)
-    B = x.shape[0]
-    groups = B // group_size if group_size > 0 else 1
-    if noise.dtype != torch.float32 or not noise.is_contiguous() or tuple(noise.shape) != (groups, *x.shape[1:]):
-        raise HipError(f"ddpm_step: noise must be contiguous f32 {(groups, *x.shape[1:])}, got "
-                       f"{noise.dtype} {tuple(noise.shape)}")
-    a.noise = noise.data_ptr()
-    kind = "ddpm_blend" if sums_bytes else "ddpm_step"
-    obs = LAUNCH_OBSERVER
-    if obs is not None and hasattr(obs, "before_aux"):
-        obs.before_aux(kind, eps.numel() * eps.element_size() + 2 * x.numel() * 4 + noise.numel() * 4 +
-                       (mask.numel() if mask is not None else 0) + sums_bytes)
-    rc = lib().p2p_ddpm_step(ctypes.byref(a), _stream(x.device))
-    if obs is not None and hasattr(obs, "after_aux"):
-        obs.after_aux(kind)
-    _check(rc, "p2p_ddpm_step")
+    a.noise = _group_rows("ddpm_step", "noise", noise, x, group_size)
+    _launch(lib().p2p_ddpm_step, "p2p_ddpm_step", a, x.device, "ddpm_blend" if sums_bytes else "ddpm_step",
+            (eps, x, out, mask, noise), sums_bytes)
     return out
 
 
-def ddpm_noise(eps, x, target, coef, guidance: float, noise):
-    """p2p_ddpm_noise for R rows: eps [2R, ...] (f32 / bf16 / f16, uncond block first), x / target /
-    noise f32 [R, ...] of eps's row shape, coef f32 [R, 5] on the device (each row's ddpm_coeffs).
-    noise[r] = (target[r] - mu(guided eps[r], x[r])) / sigma[r], zeros where sigma[r] is 0.  Launches
-    on the current stream."""
-    _require_cuda(eps, x, target, coef, noise)
+def _row_pass(what, a, out_name, width, eps, x, target, coef, guidance, out, observed):
+    """p2p_<what> for R rows (a: its empty argument struct): eps [2R, ...] (f32 / bf16 / f16, uncond
+    block first), x / target / out f32 [R, ...] of eps's row shape, coef f32 [R, width] on the
+    device.  Launches on the current stream."""
+    _require_cuda(eps, x, target, coef, out)
     R = x.shape[0]
     n = x.numel() // max(R, 1)
-    _dense("ddpm_noise eps", eps, eps.dtype, 2 * R * n)
-    for name, t in (("x", x), ("target", target), ("noise", noise)):
-        _dense(f"ddpm_noise {name}", t, torch.float32, R * n)
-    _dense("ddpm_noise coef", coef, torch.float32, 5 * R)
-    a = DdpmNoiseArgs()
+    _dense(f"{what} eps", eps, eps.dtype, 2 * R * n)
+    for name, t in (("x", x), ("target", target), (out_name, out)):
+        _dense(f"{what} {name}", t, torch.float32, R * n)
+    _dense(f"{what} coef", coef, torch.float32, width * R)
     a.eps, a.eps_dtype, a.guidance = eps.data_ptr(), _dtype_code(eps), float(guidance)
-    a.x, a.target, a.coef, a.noise = x.data_ptr(), target.data_ptr(), coef.data_ptr(), noise.data_ptr()
+    a.x, a.target, a.coef = x.data_ptr(), target.data_ptr(), coef.data_ptr()
+    setattr(a, out_name, out.data_ptr())
     a.R, a.n = R, n
-    obs = LAUNCH_OBSERVER
-    if obs is not None and hasattr(obs, "before_aux"):
-        obs.before_aux("ddpm_noise", eps.numel() * eps.element_size() + 3 * x.numel() * 4 + coef.numel() * 4)
-    rc = lib().p2p_ddpm_noise(ctypes.byref(a), _stream(x.device))
-    if obs is not None and hasattr(obs, "after_aux"):
-        obs.after_aux("ddpm_noise")
-    _check(rc, "p2p_ddpm_noise")
-    return noise
+    _launch(getattr(lib(), f"p2p_{what}"), f"p2p_{what}", a, x.device, what if observed else None,
+            (eps, x, target, out, coef))
+    return out
+
+
+def direct_offset(eps, x, target, coef, guidance: float, offset):
+    """p2p_direct_offset for R rows (see _row_pass), coef f32 [R, 4]: each row's prev_coeffs.
+    offset[r] = target[r] - prev_step(guided eps[r], x[r])."""
+    return _row_pass("direct_offset", DirectOffsetArgs(), "offset", 4, eps, x, target, coef, guidance, offset, False)
+
+
+def ddpm_noise(eps, x, target, coef, guidance: float, noise):
+    """p2p_ddpm_noise for R rows (see _row_pass), coef f32 [R, 5]: each row's ddpm_coeffs.
+    noise[r] = (target[r] - mu(guided eps[r], x[r])) / sigma[r], zeros where sigma[r] is 0.  The one of
+    the two that reports to LAUNCH_OBSERVER ("ddpm_noise")."""
+    return _row_pass("ddpm_noise", DdpmNoiseArgs(), "noise", 5, eps, x, target, coef, guidance, noise, True)
 
 
 def attn_fwd_lse(q, k, v, o, heads, scale, lse):

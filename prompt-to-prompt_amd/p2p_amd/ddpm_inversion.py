@@ -42,7 +42,7 @@ from __future__ import annotations
 import torch
 
 from .ddim import DDIMScheduler
-from .null_text import GUIDANCE_SCALE, NUM_DDIM_STEPS, NullInversion, load_512
+from .null_text import GUIDANCE_SCALE, NUM_DDIM_STEPS, NullInversion, _rows_call, load_512
 
 
 class DDPMInversion(NullInversion):
@@ -158,7 +158,11 @@ class DDPMInversion(NullInversion):
             t2 = torch.cat([t_rows, t_rows]).to(dev)
             if n not in calls:
                 ctx = torch.cat([null.repeat(n, 1, 1), cond.repeat(n, 1, 1)])
-                calls[n] = self._noise_call(x, ctx, t2) if fused else ctx
+                calls[n] = ctx
+                if fused:
+                    from . import _hip
+                    calls[n] = _rows_call(self.model.unet, self.guidance_scale, self.use_graphs, _hip.ddpm_noise,
+                                          5, x, ctx, t2)
             if fused:
                 coef = torch.tensor([self._coeffs(i) for i in steps], dtype=torch.float32)
                 z = calls[n](x, target, t2, coef.repeat_interleave(B, 0).to(dev))
@@ -175,59 +179,3 @@ class DDPMInversion(NullInversion):
                 mu = self.scheduler.ddpm_mean(e, ts[i], x[rows], self.eta)
                 out[i] = (target[rows] - mu) / torch.tensor(sigma, dtype=torch.float32, device=dev)
         return out
-
-    def _noise_call(self, x, ctx, t2):
-        """One call of the pass on x's shape: f(x, target, t2, coef) -> noise [R, 4, h, w] (valid until
-        the next call of f), a captured graph with ``use_graphs``."""
-        from . import _hip
-        unet, g = self.model.unet, self.guidance_scale
-        if self.use_graphs:
-            return _GraphedNoise(unet, x, ctx, t2, g)
-
-        def call(x, target, t2, coef):
-            eps = unet(torch.cat([x, x]), t2, encoder_hidden_states=ctx)["sample"]
-            return _hip.ddpm_noise(eps.contiguous(), x.contiguous(), target.contiguous(), coef, g,
-                                   torch.empty_like(x))
-        return call
-
-
-class _GraphedNoise:
-    """One call of the noise-map pass captured as a HIP graph, in the manner of
-    direct_inversion._GraphedOffsets: the U-Net on [x, x] with per-row timesteps, then p2p_ddpm_noise,
-    whose five factors per row are read from device memory.  __call__ refills the static levels,
-    targets, timesteps and factors and replays; the context of a pass never changes and is filled
-    once."""
-
-    def __init__(self, unet, x, ctx, t2, guidance):
-        from . import _hip
-        dev = x.device
-        self.x = x.detach().clone().contiguous()
-        self.target = torch.zeros_like(self.x)
-        self.ctx = ctx.detach().clone()
-        self.t = t2.detach().clone()
-        self.coef = torch.ones((self.x.shape[0], 5), dtype=torch.float32, device=dev)
-        self.noise = torch.empty_like(self.x)
-
-        def body():
-            eps = unet(torch.cat([self.x, self.x]), self.t, encoder_hidden_states=self.ctx)["sample"]
-            _hip.ddpm_noise(eps.contiguous(), self.x, self.target, self.coef, guidance, self.noise)
-
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.no_grad():
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    body()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                body()
-
-    @torch.no_grad()
-    def __call__(self, x, target, t2, coef):
-        self.x.copy_(x)
-        self.target.copy_(target)
-        self.t.copy_(t2)
-        self.coef.copy_(coef)
-        self.graph.replay()
-        return self.noise

@@ -25,7 +25,7 @@ from __future__ import annotations
 import torch
 
 from .ddim import DDIMScheduler
-from .null_text import GUIDANCE_SCALE, NUM_DDIM_STEPS, NullInversion, _GraphedForward, load_512
+from .null_text import GUIDANCE_SCALE, NUM_DDIM_STEPS, NullInversion, _GraphedForward, _rows_call, load_512
 
 
 class DirectInversion(NullInversion):
@@ -136,7 +136,11 @@ class DirectInversion(NullInversion):
             t2 = torch.cat([t_rows, t_rows]).to(dev)
             if n not in calls:
                 ctx = torch.cat([null.repeat(n, 1, 1), cond.repeat(n, 1, 1)])
-                calls[n] = self._offsets_call(x, ctx, t2) if fused else ctx
+                calls[n] = ctx
+                if fused:
+                    from . import _hip
+                    calls[n] = _rows_call(self.model.unet, self.guidance_scale, self.use_graphs, _hip.direct_offset,
+                                          4, x, ctx, t2)
             if fused:
                 coef = torch.tensor([self.scheduler.prev_coeffs(ts[i]) for i in steps], dtype=torch.float32)
                 off = calls[n](x, target, t2, coef.repeat_interleave(B, 0).to(dev))
@@ -149,58 +153,3 @@ class DirectInversion(NullInversion):
                 noise = eps_u[rows] + self.guidance_scale * (eps_c[rows] - eps_u[rows])
                 out[i] = target[rows] - self.prev_step(noise, ts[i], x[rows])
         return out
-
-    def _offsets_call(self, x, ctx, t2):
-        """One offsets call on x's shape: f(x, target, t2, coef) -> offset [R, 4, h, w] (valid until
-        the next call of f), a captured graph with ``use_graphs``."""
-        from . import _hip
-        unet, g = self.model.unet, self.guidance_scale
-        if self.use_graphs:
-            return _GraphedOffsets(unet, x, ctx, t2, g)
-
-        def call(x, target, t2, coef):
-            eps = unet(torch.cat([x, x]), t2, encoder_hidden_states=ctx)["sample"]
-            return _hip.direct_offset(eps.contiguous(), x.contiguous(), target.contiguous(), coef, g,
-                                      torch.empty_like(x))
-        return call
-
-
-class _GraphedOffsets:
-    """One call of the offsets pass captured as a HIP graph, in the manner of _GraphedForward: the
-    U-Net on [x, x] with per-row timesteps, then p2p_direct_offset, whose DDIM coefficients are read
-    from device memory.  __call__ refills the static latents, targets, timesteps and coefficients
-    and replays; the context of a pass never changes and is filled once."""
-
-    def __init__(self, unet, x, ctx, t2, guidance):
-        from . import _hip
-        dev = x.device
-        self.x = x.detach().clone().contiguous()
-        self.target = torch.zeros_like(self.x)
-        self.ctx = ctx.detach().clone()
-        self.t = t2.detach().clone()
-        self.coef = torch.ones((self.x.shape[0], 4), dtype=torch.float32, device=dev)
-        self.offset = torch.empty_like(self.x)
-
-        def body():
-            eps = unet(torch.cat([self.x, self.x]), self.t, encoder_hidden_states=self.ctx)["sample"]
-            _hip.direct_offset(eps.contiguous(), self.x, self.target, self.coef, guidance, self.offset)
-
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.no_grad():
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    body()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                body()
-
-    @torch.no_grad()
-    def __call__(self, x, target, t2, coef):
-        self.x.copy_(x)
-        self.target.copy_(target)
-        self.t.copy_(t2)
-        self.coef.copy_(coef)
-        self.graph.replay()
-        return self.offset

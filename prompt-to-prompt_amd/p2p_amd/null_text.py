@@ -597,6 +597,60 @@ class _GraphedForward:
         return self.out
 
 
+def _rows_call(unet, guidance, use_graphs, row_fn, width, x, ctx, t2):
+    """One call of an inversion's row pass on x's shape -- the U-Net on [x, x] with per-row timesteps,
+    then ``row_fn`` (_hip.direct_offset or _hip.ddpm_noise) with ``width`` coefficients per row:
+    f(x, target, t2, coef) -> rows [R, 4, h, w] (valid until the next call of f), a captured graph
+    with ``use_graphs``."""
+    if use_graphs:
+        return _GraphedRows(unet, x, ctx, t2, guidance, row_fn, width)
+
+    def call(x, target, t2, coef):
+        eps = unet(torch.cat([x, x]), t2, encoder_hidden_states=ctx)["sample"]
+        return row_fn(eps.contiguous(), x.contiguous(), target.contiguous(), coef, guidance, torch.empty_like(x))
+    return call
+
+
+class _GraphedRows:
+    """One call of a row pass (_rows_call) captured as a HIP graph, in the manner of _GraphedForward:
+    the U-Net on [x, x] with per-row timesteps, then the row kernel, whose coefficients are read from
+    device memory.  __call__ refills the static latents, targets, timesteps and coefficients and
+    replays; the context of a pass never changes and is filled once."""
+
+    def __init__(self, unet, x, ctx, t2, guidance, row_fn, width):
+        dev = x.device
+        self.x = x.detach().clone().contiguous()
+        self.target = torch.zeros_like(self.x)
+        self.ctx = ctx.detach().clone()
+        self.t = t2.detach().clone()
+        self.coef = torch.ones((self.x.shape[0], width), dtype=torch.float32, device=dev)
+        self.rows = torch.empty_like(self.x)
+
+        def body():
+            eps = unet(torch.cat([self.x, self.x]), self.t, encoder_hidden_states=self.ctx)["sample"]
+            row_fn(eps.contiguous(), self.x, self.target, self.coef, guidance, self.rows)
+
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.no_grad():
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    body()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                body()
+
+    @torch.no_grad()
+    def __call__(self, x, target, t2, coef):
+        self.x.copy_(x)
+        self.target.copy_(target)
+        self.t.copy_(t2)
+        self.coef.copy_(coef)
+        self.graph.replay()
+        return self.rows
+
+
 class _GraphedNullStep:
     """One null-text Adam step captured as a HIP graph (NullInversion._null_optimization_graphed).
     Static inputs: the latent, eps_c, the target latent, the timestep and the four DDIM

@@ -262,7 +262,7 @@ def _launch_latent_step(sched, mask_fn, eps, x, src, out, t, guidance_scale, pla
 
 
 def _blend_launch_ok(x, out, eps, folded, more=()) -> bool:
-    """The one-launch LocalBlend's preconditions (p2p_blend.hip run_latent_step, include/p2p_hip.h):
+    """The one-launch LocalBlend's preconditions (p2p_latent.hip check_latent_args, include/p2p_hip.h):
     whole 4-pixel vectors (H*W % 4 == 0), 16-byte aligned x / out / eps (and ``more``: the PLMS
     or DPM-Solver++ history tensors), and a latent at least as large as the map resolution (the
     3x3-pooled map is nearest-upsampled onto it)."""

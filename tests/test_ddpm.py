@@ -107,6 +107,7 @@ _FOLD = {("blend_sums", 0): 1 << 26, "blend_lh": 40, "blend_res": 16}
     ({**_FOLD, "noise": NZ + 4}, E_ARG),
     ({**_FOLD, "blend_res": 17}, E_ARG),
     ({("blend_sums", 3): 1 << 26, "blend_lh": 40, "blend_res": 16}, E_ARG),
+    (dict(noise=None, eps_dtype=7), E_ARG),                  # two faults: a NULL noise is answered first
 ])
 def test_ddpm_step_rejects(kw, code):
     """Every case returns before any launch (the pointers are not memory: a launch would fault).  That

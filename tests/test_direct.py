@@ -96,6 +96,8 @@ _FOLD = {("blend_sums", 0): 1 << 26, "blend_lh": 40, "blend_res": 16}
     ({**_FOLD, "offset": OFF + 4}, E_ARG),
     ({**_FOLD, "blend_res": 17}, E_ARG),
     ({("blend_sums", 3): 1 << 26, "blend_lh": 40, "blend_res": 16}, E_ARG),
+    (dict(offset=None, eps_dtype=7), E_ARG),                 # two faults: a NULL offset is answered first ...
+    (dict(offset=X, eps_dtype=7), E_DTYPE),                  # ... an overlapping one after the dtype
 ])
 def test_direct_step_rejects(kw, code):
     """Every case returns before any launch (the pointers are not memory: a launch would fault)."""

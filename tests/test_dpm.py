@@ -323,6 +323,7 @@ _FOLD = {("blend_sums", 0): 1 << 20, "blend_lh": 40, "blend_res": 16}
     ({**_FOLD, "hist_out": 65540}, -1),
     ({**_FOLD, "blend_res": 17}, -1),                # res^2 > 256
     ({("blend_sums", 3): 1 << 20, "blend_lh": 40, "blend_res": 16}, -1),     # a group past the batch
+    (dict(n_hist=2, eps_dtype=7), -3),               # two faults: the dtype is answered before the history
 ])
 def test_dpm_step_rejects(kw, code):
     """Every case returns before any launch (the pointers are not memory: a launch would fault)."""

@@ -122,7 +122,7 @@ def test_dpm_step_ragged_in_place_no_cfg(cuda):
 
 # ------------------------------------------------------------------ 2. the one-launch LocalBlend form
 @pytest.mark.parametrize("call", [0, 2], ids=["first_order", "second_order"])
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
 @pytest.mark.parametrize("sub", [False, True], ids=["nosub", "substruct"])
 @pytest.mark.parametrize("groups", [(True,), (True, False, True)], ids=["one_group", "three_groups"])
 def test_dpm_step_builds_folded_blend_mask(cuda, call, dtype, sub, groups):

@@ -103,7 +103,7 @@ def test_plms_step_in_place_no_cfg_ragged(cuda):
 
 # ------------------------------------------------------------------ 2. the one-launch LocalBlend form
 @pytest.mark.parametrize("call", [5, 1], ids=["call5", "corrector"])
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
 @pytest.mark.parametrize("sub", [False, True], ids=["nosub", "substruct"])
 @pytest.mark.parametrize("groups", [(True,), (True, False, True)], ids=["one_group", "three_groups"])
 def test_plms_step_builds_folded_blend_mask(cuda, call, dtype, sub, groups):

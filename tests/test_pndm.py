@@ -250,6 +250,7 @@ def _args(kw):
     ({("blend_sums", 0): 1 << 20, "blend_lh": 40, "blend_res": 16, ("hist", 2): 32772}, -1),
     ({("blend_sums", 0): 1 << 20, "blend_lh": 40, "blend_res": 16, "hist_out": 65540}, -1),
     ({("blend_sums", 3): 1 << 20, "blend_lh": 40, "blend_res": 16}, -1),     # a group past the batch
+    (dict(n_hist=5, eps_dtype=7), -3),               # two faults: the dtype is answered before the history
 ])
 def test_plms_step_rejects(kw, code):
     assert _hip.lib().p2p_plms_step(ctypes.byref(_args(kw)), None) == code

@@ -7,7 +7,7 @@ B = 4 prompts, 4 x 64 x 64 latents, bf16 eps, folded word sums [4, 2, 40, 256]:
               read, the new one written)
 then, one line per batch ([4, 4, 64, 64] and [32, 4, 64, 64]), p2p_dpm_step against p2p_plms_step in
 alternated rounds (plms_vs_dpm).
-Usage: python tools/latent_bench.py [iters]   (run under rocprofv3 --kernel-trace --stats for kernel times)"""
+Usage: python tools/latent_bench.py [iters] [bf16|f16|f32]   (the eps dtype, bf16 by default; run under rocprofv3 --kernel-trace --stats for kernel times)"""
 import json
 import os
 import sys
@@ -33,11 +33,11 @@ def timed(fn, iters):
     return s.elapsed_time(e) * 1e3 / iters
 
 
-def main(iters=200):
+def main(iters=200, dtype=torch.bfloat16):
     dev = "cuda"
     B, H, L = 4, 8, 5
     g = torch.Generator(device=dev).manual_seed(0)
-    eps = torch.randn(2 * B, 4, 64, 64, device=dev, generator=g).to(torch.bfloat16)
+    eps = torch.randn(2 * B, 4, 64, 64, device=dev, generator=g).to(dtype)
     x = torch.randn(B, 4, 64, 64, device=dev, generator=g)
     out = torch.empty_like(x)
     s = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", clip_sample=False,
@@ -65,10 +65,10 @@ def main(iters=200):
     r["plms_plain_us"] = timed(lambda: _hip.plms_step(eps, x, out, plan, 7.5, None, hist=hist, hist_out=slot), iters)
     print(json.dumps({k: round(v, 2) for k, v in r.items()}), flush=True)
     for groups in (1, 8):
-        print(json.dumps(plms_vs_dpm(dev, groups, iters)), flush=True)
+        print(json.dumps(plms_vs_dpm(dev, groups, iters, dtype=dtype)), flush=True)
 
 
-def plms_vs_dpm(dev, groups, iters, rounds=5):
+def plms_vs_dpm(dev, groups, iters, rounds=5, dtype=torch.bfloat16):
     """p2p_dpm_step (a second-order call: one stored x0 read, the new one written) against
     p2p_plms_step (call 5: three stored eps read, the new one written) of the same build, on the
     batch of ``groups`` edit groups, plain and one-launch LocalBlend form: ``rounds`` alternated
@@ -79,7 +79,7 @@ def plms_vs_dpm(dev, groups, iters, rounds=5):
     gs, H, L = 4, 8, 5
     B = groups * gs
     g = torch.Generator(device=dev).manual_seed(1)
-    eps = torch.randn(2 * B, 4, 64, 64, device=dev, generator=g).to(torch.bfloat16)
+    eps = torch.randn(2 * B, 4, 64, 64, device=dev, generator=g).to(dtype)
     x = torch.randn(B, 4, 64, 64, device=dev, generator=g)
     out = torch.empty_like(x)
     maps = [torch.zeros(gs * H, 256, 77, device=dev) for _ in range(L)]
@@ -114,4 +114,5 @@ def plms_vs_dpm(dev, groups, iters, rounds=5):
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 200)
+    main(int(sys.argv[1]) if len(sys.argv) > 1 else 200,
+         {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[sys.argv[2] if len(sys.argv) > 2 else "bf16"])
