@@ -179,6 +179,46 @@ const char* p2p_self_attn_kernel(const p2p_attn_tensors* t, int32_t keeps_maps, 
 const char* p2p_cross_attn_kernel(const p2p_attn_tensors* t, const p2p_group* groups,
                                   int32_t n_groups, int32_t any_store);
 
+/* Mutual self-attention (MasaCtrl, Cao et al. 2023, §3.2-3.3).  n_query == n_key.
+ *   s = kv_src[n]  (host, n_batch entries, NULL = identity);  s < 0: entry n is skipped, o[n] keeps its bits
+ *   O[n] = softmax(Q[n] K[s]^T * scale + M) V[s]
+ * token_class (device, nullable): uint8 [n_batch, n_query], 0 or 1 per token.  For s != n and a
+ * non-null token_class, key j is admitted for query p iff token_class[s][j] == token_class[n][p];
+ * a query whose class has NO key in entry s admits every key (unrestricted attention, never a
+ * uniform or NaN row).  M = 0 on admitted keys, -inf elsewhere.  s == n: plain self-attention.
+ * Rejected before anything is launched or dereferenced: a null operand or n_query != n_key
+ * (P2P_E_ARG), kv_src[n] >= n_batch or n_batch > P2P_MAX_BATCH (P2P_E_BATCH), and what
+ * p2p_self_attn_fwd rejects for the same tensors (the operand layout contract above, batch stride
+ * 0 and fused-projection views included).  O only: nothing is stored, no lse.  Every precision and
+ * every compiled head dim.  (Additive; ABI 16.) */
+int p2p_mutual_attn_fwd(const p2p_attn_tensors* t, const int32_t* kv_src,
+                        const uint8_t* token_class, p2p_stream_t stream);
+/* The kernel p2p_mutual_attn_fwd would launch (csrc/p2p_select.h, select_mutual), as
+ * p2p_self_attn_kernel reports the self kernels; masked: the call carries token classes. */
+const char* p2p_mutual_attn_kernel(const p2p_attn_tensors* t, int32_t masked);
+
+/* The token classes p2p_mutual_attn_fwd reads, from the running word sums the cross store epilogue
+ * folds (p2p_group.blend_sums with a one-hot alpha row on the object word(s) of each prompt).  Per
+ * prompt b of group g: the mean over the lh maps of plane 0 (sums[g][b][0][l][*], in index order),
+ * min-max normalised over the res^2 pixels, class = (value >= threshold); a constant map (max ==
+ * min) is class 0 everywhere.  The res x res classes are nearest-resized to each side[r] and
+ * written to row n_groups * group_size * cfg + g * group_size + b of out[r] (uint8 [n_batch,
+ * side[r]^2]) and, with cfg = 1, to row g * group_size + b as well: the uncond entry of a prompt
+ * gets its cond entry's row.  No host read, no allocation: capture-safe.
+ * Rejected before the launch: a null pointer, n_groups outside [1, P2P_MAX_GROUPS], group_size,
+ * lh or res < 1, res^2 > 1024, n_res outside [1, 3], a side outside [1, 1024], a NaN threshold
+ * (P2P_E_ARG); more than P2P_MAX_BATCH rows (P2P_E_BATCH); sums off 4 bytes (P2P_E_ALIGN). */
+typedef struct {
+  const float* sums[P2P_MAX_GROUPS]; /* per group [group_size, 2, lh, res^2] f32 (plane 0 is read) */
+  int32_t n_groups, group_size, lh, res;
+  float threshold;
+  int32_t cfg;                       /* 1: out has the uncond rows in front of the cond rows   */
+  int32_t n_res;
+  int32_t side[3];
+  uint8_t* out[3];
+} p2p_token_classes_args;
+int p2p_token_classes(const p2p_token_classes_args* a, p2p_stream_t stream);
+
 /* Materialise mode, for controllers that override forward(attn, ...) (the reference
  * protocol, main.py:85-98): probs[n*H + h] = softmax(Q K^T * scale) as an f32
  * [n_batch * n_heads, n_query, n_key] tensor (ptp_utils.py:195-204).  key_mask (nullable,

@@ -183,6 +183,28 @@ int fill_self_lse(SelfArgs& a, const p2p_attn_tensors* t, float* lse) {
   return check_layout(t, true, true, true, true);
 }
 
+// p2p_mutual_attn_fwd's arguments, validated, as the kernel's MutualArgs
+int fill_mutual(MutualArgs& a, const p2p_attn_tensors* t, const int32_t* kv_src, const uint8_t* token_class) {
+  int rc = check_tensors(t, true, true, true, true);
+  if (rc) return rc;
+  if (t->n_query != t->n_key) return P2P_E_ARG;
+  a.q = t->q; a.k = t->k; a.v = t->v; a.o = t->o;
+  a.ldq = t->q_row_stride; a.ldk = t->k_row_stride; a.ldv = t->v_row_stride; a.ldo = t->o_row_stride;
+  a.bsq = t->q_batch_stride; a.bsk = t->k_batch_stride; a.bsv = t->v_batch_stride; a.bso = t->o_batch_stride;
+  a.N = t->n_batch; a.P = t->n_query; a.K = t->n_key; a.H = t->n_heads;
+  a.scale_log2 = t->scale * 1.4426950408889634f;
+  a.n_qtiles = 0;
+  a.token_class = token_class;
+  a.n_active = 0;
+  for (int n = 0; n < t->n_batch; ++n) {
+    const int s = kv_src ? kv_src[n] : n;
+    if (s >= t->n_batch) return P2P_E_BATCH;
+    a.kv_src[n] = s < 0 ? -1 : s;
+    if (s >= 0) a.ent[a.n_active++] = n;
+  }
+  return check_layout(t, true, true, true, true);
+}
+
 // p2p_cross_attn_fwd's arguments, validated, as the kernels' CrossArgs
 int fill_cross(CrossArgs& a, const p2p_attn_tensors* t, const p2p_group* groups, int32_t n_groups, float* store,
                const int32_t* store_slot, int32_t store_accumulate) {
@@ -289,6 +311,26 @@ const char* p2p_self_attn_kernel(const p2p_attn_tensors* t, int32_t keeps_maps, 
   if (rc) return nullptr;
   const int sel = select_self(a, t->io_dtype, t->compute, t->head_dim, MODE_FUSED_);
   return sel < 0 ? nullptr : name((SelfKernel)sel);
+}
+
+int p2p_mutual_attn_fwd(const p2p_attn_tensors* t, const int32_t* kv_src, const uint8_t* token_class,
+                        p2p_stream_t stream) {
+  MutualArgs a;
+  const int rc = fill_mutual(a, t, kv_src, token_class);
+  if (rc) return rc;
+  return run_mutual(a, t->io_dtype, t->compute, t->head_dim, (hipStream_t)stream);
+}
+
+const char* p2p_mutual_attn_kernel(const p2p_attn_tensors* t, int32_t masked) {
+  MutualArgs a;
+  if (fill_mutual(a, t, nullptr, nullptr)) return nullptr;
+  const int sel = select_mutual(t->io_dtype, t->compute, t->head_dim, a.P, masked != 0);
+  return sel < 0 ? nullptr : name((MutualKernel)sel);
+}
+
+int p2p_token_classes(const p2p_token_classes_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_token_classes(*a, (hipStream_t)stream);
 }
 
 int p2p_cross_attn_fwd(const p2p_attn_tensors* t, const p2p_group* groups, int32_t n_groups, float* store,

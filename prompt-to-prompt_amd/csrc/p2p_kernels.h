@@ -54,6 +54,23 @@ struct SelfArgs {
   int map_entry[P2P_MAX_BATCH];  // self_maps_kernel: the stored entries (store_slot >= 0)
 };
 
+// mutual_attn_kernel (p2p_mutual.hip): its own arguments, SelfArgs stays as it is
+struct MutualArgs {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  int64_t ldq, ldk, ldv, ldo;  // token strides (elements)
+  int64_t bsq, bsk, bsv, bso;  // batch strides (elements)
+  int N, P, K, H;              // (P == K)
+  float scale_log2;
+  int n_qtiles;                // launcher-filled
+  const uint8_t* token_class;  // optional [N, P], 0 or 1 per token
+  int n_active;                // entries in ent
+  int ent[P2P_MAX_BATCH];      // the entries that run (kv_src >= 0), ascending
+  int kv_src[P2P_MAX_BATCH];   // per entry: whose K and V it reads, -1 = skipped
+};
+
 struct CrossArgs {
   const void* q;
   const void* k;
@@ -117,6 +134,10 @@ int launch_self40(const SelfArgs& a, SelfKernel k, hipStream_t st);
 int launch_self_split(const SelfArgs& a, SelfKernel k, hipStream_t st);
 // self_wide_kernel (p2p_selfwide.hip): d = 512, bf16 / fp16 inputs, O only
 int launch_self_wide(const SelfArgs& a, int prec, hipStream_t st);
+// mutual_attn_kernel (p2p_mutual.hip): select_mutual, then launch; and the token classes it reads
+int run_mutual(const MutualArgs& a, int io_dtype, int compute, int d, hipStream_t st);
+int launch_mutual(const MutualArgs& a, int prec, int d, MutualKernel k, hipStream_t st);
+int run_token_classes(const p2p_token_classes_args& a, hipStream_t st);   // every argument check is in here
 // AttentionStore epilogue of the self layers whose maps are kept (p2p_selfmaps.hip): p = exp2(c s -
 // lse) for the entries a.map_entry[0 .. n_maps) (a.lse filled by a preceding MODE_FUSED_ launch)
 int run_self_maps(const SelfArgs& a, int io_dtype, int compute, int d, hipStream_t st);

@@ -236,6 +236,69 @@ inline int select_self(int io_dtype, int compute, int d, int P, int K, int mode,
   return select_fused(prec, d, P, lse, maps);
 }
 
+// ---------------------------------------------------------------------------- mutual self attention
+// mutual_attn_kernel (p2p_mutual.hip), O only: M(id, key tile, waves, class-masked, name).  "…" and
+// D as in P2P_SELF_KERNELS.  (M, not X: the X rows of this file are the kernels that
+// tests/test_gpu_layouts.py runs under every operand layout; these have their layout tests in
+// tests/test_gpu_mutual.py.)
+#define P2P_MUTUAL_KERNELS(M)                                                   \
+  M(MUTUAL_32x4, 32, 4, false, "mutual_attn_kernel<…,D,32,4>")                  \
+  M(MUTUAL_32x4_MASKED, 32, 4, true, "mutual_attn_kernel<…,D,32,4,MASKED>")     \
+  M(MUTUAL_64x4, 64, 4, false, "mutual_attn_kernel<…,D,64,4>")                  \
+  M(MUTUAL_64x4_MASKED, 64, 4, true, "mutual_attn_kernel<…,D,64,4,MASKED>")     \
+  M(MUTUAL_64x8, 64, 8, false, "mutual_attn_kernel<…,D,64,8>")                  \
+  M(MUTUAL_64x8_MASKED, 64, 8, true, "mutual_attn_kernel<…,D,64,8,MASKED>")
+
+enum MutualKernel {
+#define P2P_ENUM(id, bk, w, masked, nm) id,
+  P2P_MUTUAL_KERNELS(P2P_ENUM)
+#undef P2P_ENUM
+  MUTUAL_KERNEL_COUNT
+};
+
+struct MutualKernelInfo {
+  int bk;       // keys per tile
+  int waves;
+  bool masked;  // the class predicate is compiled in
+  const char* name;
+};
+
+inline const MutualKernelInfo& mutual_info(MutualKernel k) {
+  static const MutualKernelInfo table[MUTUAL_KERNEL_COUNT] = {
+#define P2P_INFO(id, bk, w, masked, nm) {bk, w, masked, nm},
+      P2P_MUTUAL_KERNELS(P2P_INFO)
+#undef P2P_INFO
+  };
+  return table[k];
+}
+inline const char* name(MutualKernel k) { return mutual_info(k).name; }
+static_assert(MUTUAL_32x4_MASKED == MUTUAL_32x4 + 1 && MUTUAL_64x4_MASKED == MUTUAL_64x4 + 1 &&
+                  MUTUAL_64x8_MASKED == MUTUAL_64x8 + 1,
+              "MASKED follows the unmasked shape");
+
+// The kernel a mutual launch runs, or a negative P2P_E_* code.  masked: the call carries token
+// classes.  One kernel family serves every precision and every compiled head dim; its loop is
+// self_attn_fused_kernel's, so the tile and wave choice is select_fused's, whose measurements
+// (tools/attn_bench.py, profiles/) were made on that loop: fused_bk's key tile (32 keys at d >= 128
+// and for the f32 P V, else 64), 8 waves x 32 query rows at d = 40 / 80 on 64-key tiles (measured
+// best at d = 40 and within 2 % of best at d = 80 there), 4 waves elsewhere.  P <= 64 keeps 4
+// waves (select_fused takes 2): MasaCtrl's layers are the 32x32 and 64x64 ones, the small shapes
+// occur in tests only.  Measured against the production self kernels on the same tensors (at d = 40 /
+// 80 those are self40_kernel, not this loop; tools/mutual_bench.py, N = 8, H = 8, bf16, kernel time,
+// profiles/r21/mutual/mutual_bench.txt): P = 4096, d = 40: 182.1 us self, 238.0 unmasked (1.31x),
+// 298.3 / 292.0 masked with 30 % / 50 % foreground (1.64x / 1.60x); P = 1024, d = 80: 26.2 us self,
+// 31.7 unmasked (1.21x), 38.3 / 38.2 masked (1.46x); fp16 within 3 % of these.  Other wave counts
+// were not tried for this kernel.
+inline int select_mutual(int io_dtype, int compute, int d, int P, bool masked) {
+  const int prec = select_precision(io_dtype, compute);
+  if (prec < 0) return prec;
+  if (!head_dim_compiled(d)) return P2P_E_HEAD_DIM;
+  const int bk = fused_bk(d, prec != PREC_F32);
+  const int waves = (bk == 64 && (d == 40 || d == 80) && P > 64) ? 8 : 4;
+  const MutualKernel base = bk == 32 ? MUTUAL_32x4 : waves == 4 ? MUTUAL_64x4 : MUTUAL_64x8;
+  return base + (masked ? 1 : 0);
+}
+
 // ---------------------------------------------------------------------------- cross attention
 // X(id, name): the group kernel's EDIT / STORE forms, and the per-entry kernel with its waves and
 // whether the dense mapper tile is staged

@@ -82,6 +82,14 @@ class BlendArgs(ctypes.Structure):
     ]
 
 
+class TokenClassesArgs(ctypes.Structure):
+    _fields_ = [
+        ("sums", ctypes.c_void_p * MAX_GROUPS), ("n_groups", ctypes.c_int32), ("group_size", ctypes.c_int32),
+        ("lh", ctypes.c_int32), ("res", ctypes.c_int32), ("threshold", ctypes.c_float), ("cfg", ctypes.c_int32),
+        ("n_res", ctypes.c_int32), ("side", ctypes.c_int32 * 3), ("out", ctypes.c_void_p * 3),
+    ]
+
+
 # The five step argument structs (include/p2p_hip.h) share their head and their LocalBlend fields; the
 # DDIM family carries its four factors between the two, the multistep forms their history after.
 _STEP_HEAD = [
@@ -314,6 +322,7 @@ def lib():
         # every export returns int, but for these
         other = {"p2p_error_string": ctypes.c_char_p, "p2p_source_hash": ctypes.c_char_p,
                  "p2p_self_attn_kernel": ctypes.c_char_p, "p2p_cross_attn_kernel": ctypes.c_char_p,
+                 "p2p_mutual_attn_kernel": ctypes.c_char_p,
                  "p2p_attn_bwd_workspace": ctypes.c_int64, "p2p_group_norm_stats_floats": ctypes.c_int64,
                  "p2p_group_norm_bwd_workspace_floats": ctypes.c_int64,
                  "p2p_conv3x3_workspace_floats": ctypes.c_int64}
@@ -323,6 +332,9 @@ def lib():
         L.p2p_self_attn_kernel.argtypes = [ctypes.POINTER(AttnTensors), i32, i32]
         L.p2p_cross_attn_kernel.argtypes = [ctypes.POINTER(AttnTensors), vp, i32, i32]
         L.p2p_self_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp, i32, vp, vp]
+        L.p2p_mutual_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp]
+        L.p2p_mutual_attn_kernel.argtypes = [ctypes.POINTER(AttnTensors), i32]
+        L.p2p_token_classes.argtypes = [ctypes.POINTER(TokenClassesArgs), vp]
         L.p2p_cross_attn_fwd.argtypes = [ctypes.POINTER(AttnTensors), vp, i32, vp, vp, i32, vp]
         L.p2p_attn_probs.argtypes = [ctypes.POINTER(AttnTensors), vp, vp, vp]
         L.p2p_attn_pv.argtypes = [ctypes.POINTER(AttnTensors), vp, vp]
@@ -397,7 +409,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_group_norm_bwd_workspace_floats", "p2p_geglu_bwd", "p2p_nchw_to_tokens", "p2p_time_embed",
                     "p2p_time_proj", "p2p_conv3x3", "p2p_conv3x3_split", "p2p_conv3x3_workspace_floats",
                     "p2p_conv3x3_pack", "p2p_dpm_step", "p2p_direct_step", "p2p_direct_offset",
-                    "p2p_ddpm_step", "p2p_ddpm_noise")
+                    "p2p_ddpm_step", "p2p_ddpm_noise", "p2p_mutual_attn_fwd", "p2p_mutual_attn_kernel",
+                    "p2p_token_classes")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -511,6 +524,74 @@ def self_attn_kernel(t: AttnTensors, keeps_maps: bool = False, wants_lse: bool =
     the library names it (csrc/p2p_select.h), or None where it rejects them.  Launches nothing."""
     name = lib().p2p_self_attn_kernel(ctypes.byref(t), int(bool(keeps_maps)), int(bool(wants_lse)))
     return name.decode() if name is not None else None
+
+
+def mutual_attn_kernel(t: AttnTensors, masked: bool = False) -> Optional[str]:
+    """The same for p2p_mutual_attn_fwd; ``masked``: the call carries token classes."""
+    name = lib().p2p_mutual_attn_kernel(ctypes.byref(t), int(bool(masked)))
+    return name.decode() if name is not None else None
+
+
+def mutual_attn(q, k, v, o, heads, scale, kv_src, token_class=None, compute="bf16"):
+    """Mutual self-attention (p2p_mutual_attn_fwd): o[n] = softmax(q[n] k[s]^T * scale + M) v[s], s =
+    kv_src[n] (None: the identity; s < 0: o[n] is left alone).  ``token_class``: None, or a contiguous
+    uint8 [N, P] tensor of 0 / 1 on the operands' device -- for s != n a query reads only the keys of
+    its own class in entry s (every key where s holds none of that class).  Returns ``o``, or None
+    for what the library does not take (CPU tensors, a head dim without a kernel, a dtype or
+    alignment it refuses): the caller then runs its torch lines.  Any other rejection raises."""
+    if not (q.is_cuda and k.is_cuda and v.is_cuda and o.is_cuda):
+        return None
+    if q.dtype not in (torch.float32, torch.bfloat16, torch.float16) or q.shape[1] != k.shape[1]:
+        return None
+    if token_class is not None:
+        if (token_class.dtype != torch.uint8 or token_class.shape != (q.shape[0], q.shape[1])
+                or not token_class.is_contiguous() or token_class.device != q.device):
+            raise HipError(f"mutual_attn: token_class must be a contiguous uint8 {tuple(q.shape[:2])} tensor on {q.device}")
+    t = make_tensors(q, k, v, o, heads, scale, compute)
+    src = _i32_array(kv_src) if kv_src is not None else None
+    if src is not None and len(src) != t.n_batch:
+        raise HipError(f"mutual_attn: kv_src has {len(src)} entries for a batch of {t.n_batch}")
+    obs = LAUNCH_OBSERVER
+    if obs is not None:
+        info = {"stored": 0, "accumulate": False}
+        obs.before("mutual", t, info)
+    rc = lib().p2p_mutual_attn_fwd(ctypes.byref(t), src, token_class.data_ptr() if token_class is not None else None,
+                                   _stream(q.device))
+    if obs is not None:
+        obs.after("mutual", t, info)
+    if rc in (P2P_E_HEAD_DIM, P2P_E_DTYPE, P2P_E_ALIGN):
+        return None
+    _check(rc, "p2p_mutual_attn_fwd")
+    return o
+
+
+def token_classes(sums, group_size: int, lh: int, res: int, threshold: float, sides, outs, cfg: bool = True):
+    """The token classes of mutual_attn from the running word sums (p2p_token_classes).  ``sums``:
+    one contiguous f32 [group_size, 2, lh, res^2] tensor per prompt group (plane 0 is read);
+    ``outs``: one contiguous uint8 [n_batch, side^2] tensor per side of ``sides`` (up to three),
+    n_batch = groups * group_size * (2 if cfg else 1).  Fills and returns ``outs``; None for CPU
+    tensors.  One launch, no host read, no allocation."""
+    sums, sides, outs = list(sums), [int(s) for s in sides], list(outs)
+    if not all(t.is_cuda for t in sums + outs):
+        return None
+    rows = len(sums) * group_size * (2 if cfg else 1)
+    for s in sums:
+        if s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != group_size * 2 * lh * res * res:
+            raise HipError(f"token_classes: sums must be contiguous f32 [{group_size}, 2, {lh}, {res * res}]")
+    if len(sides) != len(outs) or not 1 <= len(sides) <= 3 or len(sums) > MAX_GROUPS:
+        raise HipError("token_classes: one output per side, one to three sides")
+    for side, o in zip(sides, outs):
+        if o.dtype != torch.uint8 or not o.is_contiguous() or o.shape != (rows, side * side):
+            raise HipError(f"token_classes: the output of side {side} must be a contiguous uint8 [{rows}, {side * side}]")
+    a = TokenClassesArgs()
+    for g, s in enumerate(sums):
+        a.sums[g] = s.data_ptr()
+    a.n_groups, a.group_size, a.lh, a.res = len(sums), int(group_size), int(lh), int(res)
+    a.threshold, a.cfg, a.n_res = float(threshold), int(bool(cfg)), len(sides)
+    for r, (side, o) in enumerate(zip(sides, outs)):
+        a.side[r], a.out[r] = side, o.data_ptr()
+    _check(lib().p2p_token_classes(ctypes.byref(a), _stream(outs[0].device)), "p2p_token_classes")
+    return outs
 
 
 def cross_attn_kernel(t: AttnTensors, G, any_store: bool = False) -> Optional[str]:

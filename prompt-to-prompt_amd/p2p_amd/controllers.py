@@ -21,6 +21,7 @@ protocol instead: the probabilities are materialised by a HIP kernel, handed to
 from __future__ import annotations
 
 import abc
+import os
 from collections import defaultdict
 from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
@@ -317,6 +318,15 @@ class AttentionControl(abc.ABC):
         """Whether this step's self-attention over K keys gives the edits the source's Q and K."""
         return False
 
+    def _mutual_source(self, layer: int) -> bool:
+        """Whether self-attention call ``layer`` of this step gives the edits the source's K and V
+        (MutualSelfAttentionControl)."""
+        return False
+
+    def _folds_words(self) -> bool:
+        """Whether a controller WITHOUT a cross edit folds word sums in the stored cross launches."""
+        return False
+
     def _fused_attention(self, members, group_size, q, k, v, heads, scale, is_cross, place_in_unet):
         """ONE kernel launch for the prompt groups that share this U-Net call: ``members`` holds one
         controller per group, each owning ``group_size`` prompts of the conditional half -- or, with
@@ -370,6 +380,16 @@ class AttentionControl(abc.ABC):
             slots = [-1] * n0 + [(n - n0) * heads for n in range(n0, N)]
         out = torch.empty_like(q)
         if not cross:
+            # self-attention calls so far this step: the layer index of _mutual_source
+            layer = None if is_cross else self._fused_calls["self_layer"]
+            if layer is not None:
+                self._fused_calls["self_layer"] += 1
+                mutual = [m._mutual_source(layer) for m in members]
+                if any(mutual):
+                    if store is not None or any(m._injects_source(K) for m in members):
+                        raise ValueError("mutual self-attention shares a launch neither with kept self maps nor with "
+                                         "an AttentionControlEdit's source injection")
+                    return _mutual_attention(self, members, mutual, B, n0, q, k, v, out, heads, scale)
             qk_src = None                   # (the identity)
             for g, m in enumerate(members):
                 if not is_cross and m._injects_source(K):
@@ -379,12 +399,16 @@ class AttentionControl(abc.ABC):
             _hip.self_attn(q, k, v, out, heads, scale, compute=config.COMPUTE, qk_src=qk_src, store=store,
                            store_slot=slots, accumulate=acc)
             return out
-        if batched or edits[0] is not None:
+        # a controller without a cross edit may still fold word sums (the mutual one's token classes)
+        folds = [m._blend_fold(store_key, P, K, heads, q.device) if edit is None and store is not None and m._folds_words()
+                 else None for m, edit in zip(members, edits)]
+        if batched or edits[0] is not None or folds[0] is not None:
             # the uncond rows ("" prompts) share their K / V: staged once per workgroup (SHARED_KV)
             groups = [(0, n0, None, None, None, _hip.shared_kv_hint(k, v, 0, n0))] if n0 else []
             for g, (m, edit) in enumerate(zip(members, edits)):
                 if edit is None:
-                    groups.append((n0 + g * B, B, None, None))
+                    groups.append((n0 + g * B, B, None, None) if folds[g] is None else
+                                  (n0 + g * B, B, None, None, folds[g], 0))
                     continue
                 alpha, prog, hints = edit
                 blend = m._blend_fold(store_key, P, K, heads, q.device) if store is not None else None
@@ -717,6 +741,280 @@ class AttentionReweight(AttentionControlEdit):
 AttentionReweight._P2P_LIB = True
 
 
+# ============================================================================ mutual self-attention
+# MasaCtrl (Cao et al., ICCV 2023, §3.2-3.3): the opposite of replace_self_attention.  An edit row
+# keeps its own queries and reads the SOURCE row's keys and values, which keeps the content and
+# lets the layout move; with ``ref_words`` a foreground query reads only the source's foreground
+# keys and a background query its background keys (the mask-guided form).
+MUTUAL_KERNELS = os.environ.get("P2P_MUTUAL", "1") != "0"    # 0: the torch lines below instead of p2p_mutual_attn_fwd
+MUTUAL_MAX_SIDES = 3                                         # resolutions per p2p_token_classes launch
+
+
+def mutual_attention_torch(q, k, v, heads, scale, kv_src, token_class, out):
+    """The mathematics of p2p_mutual_attn_fwd in torch lines (f32): out[n] = softmax(q[n] k[s]^T *
+    scale + M) v[s], s = kv_src[n]; s < 0 leaves out[n] alone.  With ``token_class`` (uint8 [N, P])
+    and s != n a query reads the keys of its own class in entry s, every key where s has none."""
+    N, P, C = q.shape
+    d = C // heads
+
+    def split(x, n):
+        return x[n].float().reshape(P, heads, d).transpose(0, 1)          # [H, P, d]
+    for n in range(N):
+        s = int(kv_src[n])
+        if s < 0:
+            continue
+        logits = torch.einsum("hpd,hjd->hpj", split(q, n), split(k, s)) * scale
+        if token_class is not None and s != n:
+            cq, ck = token_class[n].bool(), token_class[s].bool()
+            has = torch.stack([(~ck).any(), ck.any()])
+            admitted = (cq[:, None] == ck[None, :]) | ~has[cq.long()][:, None]
+            logits = logits.masked_fill(~admitted[None], float("-inf"))
+        o = torch.einsum("hpj,hjd->hpd", logits.softmax(-1), split(v, s))
+        out[n] = o.transpose(0, 1).reshape(P, C).to(out.dtype)
+    return out
+
+
+def token_classes_torch(sums, threshold, sides, cfg=True):
+    """The torch lines of p2p_token_classes: ``sums`` one [B, 2, lh, res^2] f32 tensor per prompt
+    group; per side a uint8 [rows, side^2] tensor, the uncond rows (cfg) a copy of the cond rows."""
+    cls = []
+    for s in sums:
+        m = s[:, 0].float().sum(1) / s.shape[2]                           # mean over the lh maps
+        mn, mx = m.min(1, keepdim=True).values, m.max(1, keepdim=True).values
+        rng = mx - mn
+        cls.append(torch.where(rng > 0, (m - mn) / rng >= threshold, torch.zeros_like(m, dtype=torch.bool)))
+    cls = torch.cat(cls, 0)
+    res = int(round(cls.shape[1] ** 0.5))
+    cls = cls.reshape(-1, res, res)
+    outs = []
+    for side in sides:
+        idx = (torch.arange(side, device=cls.device) * res) // side      # nearest: floor(dst * res / side)
+        up = cls[:, idx][:, :, idx].reshape(cls.shape[0], side * side).to(torch.uint8)
+        outs.append(torch.cat([up, up], 0) if cfg else up)
+    return outs
+
+
+def _mutual_classes(owner, members, B, N, P, device):
+    """The uint8 [N, P] token classes of this step for a mutual layer of P tokens, or None (unmasked:
+    no member has ref_words, or the word sums are not complete yet).  Built once per step, at the
+    step's first mutual layer, for every resolution a mutual layer has had so far -- one
+    p2p_token_classes launch, into tensors allocated once -- and kept on ``owner``."""
+    masked = {m._ref_alpha is not None for m in members}
+    if masked == {False}:
+        return None
+    if len(masked) > 1 or len({float(m.mask_threshold) for m in members}) > 1:
+        raise ValueError("the mutual controllers of one U-Net batch must agree on ref_words (all or none) and on mask_threshold")
+    side = int(round(P ** 0.5))
+    if side * side != P:
+        raise ValueError(f"mask-guided mutual self-attention needs a square token grid, got {P} tokens")
+    if not all(m._sums_usable() for m in members):
+        return None
+    cache = owner.__dict__.setdefault("_mutual_cls", {"step": -1, "built": set(), "sides": [], "rows": {}})
+    step = members[0].cur_step
+    if side not in cache["sides"]:
+        cache["sides"].append(side)
+    if cache["step"] != step or side not in cache["built"]:
+        sums = [m._blend_sums for m in members]
+        lh, res2 = sums[0].shape[2], sums[0].shape[3]
+        res = int(round(res2 ** 0.5))
+        for s in cache["sides"]:
+            if s not in cache["rows"] or cache["rows"][s].shape[0] != N or cache["rows"][s].device != device:
+                cache["rows"][s] = torch.empty(N, s * s, dtype=torch.uint8, device=device)
+        for i in range(0, len(cache["sides"]), MUTUAL_MAX_SIDES):
+            sides = cache["sides"][i:i + MUTUAL_MAX_SIDES]
+            outs = [cache["rows"][s] for s in sides]
+            done = None
+            if MUTUAL_KERNELS and device.type == "cuda":
+                done = _hip.token_classes(sums, B, lh, res, float(members[0].mask_threshold), sides, outs, cfg=True)
+            if done is None:
+                for o, t in zip(outs, token_classes_torch(sums, float(members[0].mask_threshold), sides, cfg=True)):
+                    o.copy_(t)
+        cache["step"], cache["built"] = step, set(cache["sides"])
+    return cache["rows"][side]
+
+
+def _mutual_attention(owner, members, mutual, B, n0, q, k, v, out, heads, scale):
+    """One mutual layer for the prompt groups of a U-Net call (AttentionControl._fused_attention):
+    in both halves the edit rows of every active group read their source row's K and V.  The source
+    rows -- with every group active the stride-B view 0, B, 2B, ... of the batch -- keep the kernel
+    a plain AttentionStore launches for them (p2p_self_attn_fwd), so the source image has the bits
+    it has without the controller; the edit rows run p2p_mutual_attn_fwd (or, with P2P_MUTUAL=0 or
+    a shape it does not take, the torch lines)."""
+    N, P = q.shape[0], q.shape[1]
+    kv_src = list(range(N))
+    for g, on in enumerate(mutual):
+        if on:
+            for half in (0, n0):
+                first = half + g * B
+                kv_src[first + 1:first + B] = [first] * (B - 1)
+    active = [m for m, on in zip(members, mutual) if on]
+    classes = _mutual_classes(owner, active, B, N, P, q.device) if len(active) == len(members) else None
+    if len(active) != len(members) and any(m._ref_alpha is not None for m in active):
+        raise ValueError("mask-guided mutual controllers of one U-Net batch must share start_step and start_layer")
+    if all(mutual) and q.is_cuda:
+        # the sources alone, on the plain kernel; the mutual launch skips them
+        _hip.self_attn(q[::B], k[::B], v[::B], out[::B], heads, scale, compute=config.COMPUTE)
+        edit_src = [-1 if s == n else s for n, s in enumerate(kv_src)]
+    else:
+        edit_src = kv_src
+    obs = MUTUAL_OBSERVER
+    if obs is not None:
+        obs(dict(q=q, k=k, v=v, out=out, heads=heads, scale=scale, kv_src=list(kv_src), edit_src=list(edit_src),
+                 token_class=classes, step=members[0].cur_step))
+    if MUTUAL_KERNELS and q.is_cuda and _hip.mutual_attn(q, k, v, out, heads, scale, edit_src, token_class=classes,
+                                           compute=config.COMPUTE) is not None:
+        return out
+    return mutual_attention_torch(q, k, v, heads, scale, edit_src, classes, out)
+
+
+# Optional: called with the operands of every mutual launch before it runs (tests record them)
+MUTUAL_OBSERVER = None
+
+
+class MutualSelfAttentionControl(AttentionStore):
+    """Mutual self-attention control (MasaCtrl): from denoising step ``start_step`` on, in the
+    self-attention layers ``start_layer`` .. (layer = self-attention calls so far in the step, 0..15
+    on the SD U-Net; the defaults are the paper's: the decoder's 32x32 and 64x64 layers), the edit
+    prompts attend to the source prompt's keys and values with their own queries, in the uncond
+    half (uncond edit rows read the uncond source row) and the cond half alike.  ``ref_words``: one
+    word or tuple of words per prompt naming its object; the cross maps of those words give each
+    token a foreground / background class (the running word sums of the five 16x16 cross layers,
+    mean over layers and heads, min-max normalised, >= ``mask_threshold``) and an edit query then
+    reads only the source keys of its own class.  None: unmasked mutual attention.
+
+    Runs on the fused kernels (one launch per layer, also for a GroupBatch of these), on the torch
+    lines for CPU tensors or with P2P_MUTUAL=0.  The probability-only ``forward(attn, ...)``
+    protocol cannot express the edit: a ``forward`` call in an active layer raises."""
+
+    _NATIVE = ("forward", "between_steps", "attention")
+    store_self_maps = False
+
+    def __init__(self, prompts, num_steps: int, start_step: int = 4, start_layer: int = 10, ref_words=None,
+                 mask_threshold: float = 0.1, tokenizer=None, device=None):
+        super().__init__()
+        self.tokenizer = tokenizer or get_tokenizer()
+        self.device = device or default_device()
+        self.batch_size = len(prompts)
+        self.num_steps, self.start_step, self.start_layer = int(num_steps), int(start_step), int(start_layer)
+        self.ref_words, self.mask_threshold = ref_words, float(mask_threshold)
+        self._ref_alpha = None
+        if ref_words is not None:
+            if len(ref_words) != len(prompts):
+                raise ValueError("ref_words needs one word (or tuple of words) per prompt")
+            alpha = _word_alpha_layers(prompts, ref_words, self.tokenizer)
+            self._ref_alpha = alpha.reshape(len(prompts), -1).contiguous().to(self.device)
+        self._blend_sums, self._blend_step, self._fold_steps = None, set(), 0
+
+    # ------------------------------------------------------------------ window
+    def _mutual_source(self, layer: int) -> bool:
+        return self.batch_size > 1 and self.cur_step >= self.start_step and layer >= self.start_layer
+
+    def forward(self, attn, is_cross: bool, place_in_unet: str):
+        if not is_cross:
+            layer = self._fused_calls["self_layer"]
+            self._fused_calls["self_layer"] += 1
+            if self._mutual_source(layer):
+                raise RuntimeError("mutual self-attention replaces keys and values: the probability-only "
+                                   "forward(attn, ...) protocol cannot express it (use attention(q, k, v, ...))")
+            return attn                     # (store_self_maps = False)
+        return super().forward(attn, is_cross, place_in_unet)
+
+    # ------------------------------------------------------------------ word sums -> classes
+    def _folds_words(self) -> bool:
+        return self._ref_alpha is not None
+
+    def _blend_fold(self, key_idx, P, K, heads, device):
+        """The p2p_group.blend_* tuple of this stored cross layer (AttentionControlEdit._blend_fold's
+        layers and layout, one-hot alpha rows on ref_words, no substruct plane), or None."""
+        slots = AttentionControlEdit.BLEND_SLOTS
+        slot = slots.get(key_idx)
+        alpha = self._ref_alpha
+        if slot is None or alpha is None or P != 256 or alpha.shape != (self.batch_size, K):
+            return None
+        if alpha.device != device:
+            alpha = self._ref_alpha = alpha.to(device)
+        lh = len(slots) * heads
+        shape = (self.batch_size, 2, lh, P)
+        if self._blend_sums is None or self._blend_sums.shape != shape or self._blend_sums.device != device:
+            self._blend_sums = torch.empty(shape, dtype=torch.float32, device=device)
+            self._fold_steps = 0
+        self._blend_step.add(slot)
+        return self._blend_sums, alpha, None, slot * heads, lh
+
+    def _sums_usable(self) -> bool:
+        """Every layer of the sums holds maps: a complete earlier step, or this step's five folds."""
+        n = len(AttentionControlEdit.BLEND_SLOTS)
+        return self._blend_sums is not None and (self._fold_steps > 0 or len(self._blend_step) == n)
+
+    def between_steps(self):
+        first = len(self.attention_store) == 0
+        complete = len(self._blend_step) == len(AttentionControlEdit.BLEND_SLOTS)
+        self._fold_steps = (1 if first else self._fold_steps + 1) if complete and (first or self._fold_steps > 0) else 0
+        self._blend_step = set()
+        super().between_steps()
+
+    def reset(self):
+        super().reset()
+        self._blend_step, self._fold_steps = set(), 0
+        self.__dict__.pop("_mutual_cls", None)
+
+    # ------------------------------------------------------------------ attention
+    def attention(self, q, k, v, heads, scale, is_cross, place_in_unet, mask=None):
+        if mask is not None:
+            raise ValueError("MutualSelfAttentionControl does not take an attention mask")
+        if _low_resource():
+            raise ValueError("MutualSelfAttentionControl does not run with LOW_RESOURCE (it edits both CFG halves "
+                             "of one U-Net call)")
+        if q.is_cuda:
+            return super().attention(q, k, v, heads, scale, is_cross, place_in_unet)
+        out = self._torch_attention(q, k, v, heads, scale, is_cross, place_in_unet)
+        self._advance_layer()
+        return out
+
+    def _torch_attention(self, q, k, v, heads, scale, is_cross, place_in_unet):
+        """The whole call in torch lines (CPU tensors): plain attention with the AttentionStore's
+        cross maps and word sums outside the window, the mutual edit inside it."""
+        N, P, C = q.shape
+        K, d = k.shape[1], C // heads
+        n0 = N // 2
+        B = N - n0
+        if B != self.batch_size:
+            raise ValueError(f"controller built for {self.batch_size} prompts got a batch of {B}")
+        out = torch.empty_like(q)
+        if not is_cross:
+            layer = self._fused_calls["self_layer"]
+            self._fused_calls["self_layer"] += 1
+            if self._mutual_source(layer):
+                return _mutual_attention(self, [self], [True], B, n0, q, k, v, out, heads, scale)
+            return mutual_attention_torch(q, k, v, heads, scale, list(range(N)), None, out)
+        qh = q.float().reshape(N, P, heads, d).transpose(1, 2)
+        kh = k.float().reshape(N, K, heads, d).transpose(1, 2)
+        vh = v.float().reshape(N, K, heads, d).transpose(1, 2)
+        probs = (torch.einsum("nhpd,nhjd->nhpj", qh, kh) * scale).softmax(-1)
+        if P <= MAX_STORED_QUERIES:
+            key = f"{place_in_unet}_cross"
+            idx = self._fused_calls[key]
+            self._fused_calls[key] += 1
+            cond = probs[n0:].reshape(B * heads, P, K)
+            first = len(self.attention_store) == 0
+            if first:
+                self.step_store[key].append(cond.clone())
+            else:
+                self.attention_store[key][idx] += cond
+            fold = self._blend_fold((key, idx), P, K, heads, q.device)
+            if fold is not None:
+                sums, alpha, _, col, _ = fold
+                words = torch.einsum("bhpw,bw->bhp", probs[n0:], alpha)
+                if first:
+                    sums[:, 0, col:col + heads] = words
+                else:
+                    sums[:, 0, col:col + heads] += words
+        return torch.einsum("nhpj,nhjd->nhpd", probs, vh).transpose(1, 2).reshape(N, P, C).to(q.dtype)
+
+
+MutualSelfAttentionControl._P2P_LIB = True
+
+
 # ============================================================================ prompt-group batching
 class GroupBatch(AttentionControl):
     """Several prompt groups -- one controller each, built exactly as for a single group -- in
@@ -751,6 +1049,10 @@ class GroupBatch(AttentionControl):
             if isinstance(m, AttentionControlEdit) and m.batch_size != self.group_size:
                 raise ValueError(f"{type(m).__name__} was built for {m.batch_size} prompts, "
                                  f"GroupBatch groups have {self.group_size}")
+        kinds = {isinstance(m, MutualSelfAttentionControl) for m in self.members}
+        if kinds == {True, False} and any(isinstance(m, AttentionControlEdit) for m in self.members):
+            raise ValueError("GroupBatch does not mix MutualSelfAttentionControl with AttentionControlEdit members: "
+                             "a self-attention launch takes the source's probabilities or its keys and values, not both")
         storing = {isinstance(m, AttentionStore) for m in self.members}
         if len(storing) != 1:
             raise ValueError("mix of storing and non-storing controllers")
@@ -773,6 +1075,7 @@ class GroupBatch(AttentionControl):
 
     def reset(self):
         super().reset()
+        self.__dict__.pop("_mutual_cls", None)
         for m in getattr(self, "members", ()):
             m.reset()
 

@@ -179,6 +179,20 @@ def make_replace_controller(prompts: Sequence[str], num_steps: int = 50, cross_r
     return ctrl
 
 
+def make_mutual_controller(prompts: Sequence[str], num_steps: int = 50, start_step: int = 4, start_layer: int = 10,
+                           ref_words=None, mask_threshold: float = 0.1, device=None, tokenizer=None):
+    """A controllers.MutualSelfAttentionControl (MasaCtrl) for 1 source + edits: non-rigid edits --
+    the edits keep the source's content (its self-attention keys and values) under their own
+    layout.  ``ref_words``: one word or tuple of words per prompt for the mask-guided form, e.g.
+    ``("squirrel", "squirrel")``.  Works with run_edit_group, run_edit_groups (a GroupBatch of
+    these) and edit_batch_runner / GraphedEditRunner, and on inverted latents through
+    ptp_utils.text2image_ldm_stable(latent=..., latent_offsets=... | latent_noise=...)."""
+    from . import controllers
+    return controllers.MutualSelfAttentionControl(list(prompts), num_steps, start_step=start_step,
+                                                  start_layer=start_layer, ref_words=ref_words,
+                                                  mask_threshold=mask_threshold, tokenizer=tokenizer, device=device)
+
+
 @torch.no_grad()
 def run_edit_group(model: SyntheticStableDiffusion, prompts: Sequence[str], controller, x_T: torch.Tensor,
                    num_steps: int = 50, guidance_scale: float = 7.5):
