@@ -634,6 +634,38 @@ int p2p_conv3x3_split(int32_t n, int32_t height, int32_t width, int32_t c_in, in
 /* f32 elements p2p_conv3x3 needs behind `workspace` (0 without a split), or the P2P_E_* code. */
 int64_t p2p_conv3x3_workspace_floats(int32_t n, int32_t height, int32_t width, int32_t c_in, int32_t c_out);
 
+/* p2p_conv3x3_ex: the same kernel with a sampling form and an optional bias (additive to ABI 16).
+ *   P2P_CONV_SAME   stride 1, padding 1: p2p_conv3x3 (which forwards here with a null bias);
+ *   P2P_CONV_UP2    F.interpolate(scale_factor=2, mode="nearest") followed by the padded stride-1
+ *                   convolution, the upsampled map never written: x is the low-resolution map, y
+ *                   is 2 in_height x 2 in_width;
+ *   P2P_CONV_DOWN2  stride 2, padding 1, even in_height and in_width: y is in_height / 2 x in_width / 2.
+ * x is token-major [n, in_height * in_width, c_in], y NCHW on the output map, `weight` the image of
+ * p2p_conv3x3_pack for every form.  bias: [c_out] in the tensors' dtype or NULL; it is added to the
+ * f32 accumulator (in the split form to the sum of the partials) before the one rounding, and with
+ * NULL the bits are those of the call without it.  The checks and codes are p2p_conv3x3's, on the
+ * output map and on x's element count: also an unknown form (P2P_E_ARG), a bias off 2 bytes and odd
+ * input sizes for P2P_CONV_DOWN2 (P2P_E_ALIGN). */
+enum { P2P_CONV_SAME = 0, P2P_CONV_UP2 = 1, P2P_CONV_DOWN2 = 2 };
+
+typedef struct {
+  const void* x;       /* [n, in_height * in_width, c_in]                                      */
+  const void* weight;  /* [9, c_out, c_in], from p2p_conv3x3_pack                              */
+  const void* bias;    /* [c_out] or NULL                                                      */
+  void* y;             /* [n, c_out, out_height * out_width]                                   */
+  float* workspace;    /* p2p_conv3x3_ex_workspace_floats() f32; may be NULL where that is 0   */
+  int32_t n, in_height, in_width, c_in, c_out;
+  int32_t dtype;       /* P2P_DTYPE_BF16 / P2P_DTYPE_F16: x, weight, bias and y                */
+  int32_t form;        /* P2P_CONV_*                                                           */
+} p2p_conv3x3_ex_args;
+
+int p2p_conv3x3_ex(const p2p_conv3x3_ex_args* a, p2p_stream_t stream);
+/* p2p_conv3x3_split / _workspace_floats for a form, from the input map: the split comes from the
+ * output map exactly as p2p_conv3x3_split's does; 0 = not served, or the P2P_E_* code. */
+int p2p_conv3x3_ex_split(int32_t form, int32_t n, int32_t in_height, int32_t in_width, int32_t c_in, int32_t c_out);
+int64_t p2p_conv3x3_ex_workspace_floats(int32_t form, int32_t n, int32_t in_height, int32_t in_width, int32_t c_in,
+                                        int32_t c_out);
+
 /* packed[tap, co, ci] = weight[co, ci, tap / 3, tap % 3]: the K-major image p2p_conv3x3 stages.
  * c_in % 32 and c_out % 32, packed on 16 bytes (else P2P_E_ALIGN). */
 typedef struct {

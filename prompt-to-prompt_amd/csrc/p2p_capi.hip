@@ -523,6 +523,28 @@ int64_t p2p_conv3x3_workspace_floats(int32_t n, int32_t height, int32_t width, i
   return rc < 0 ? rc : conv3x3_workspace_floats(n, height, width, c_in, c_out);
 }
 
+int p2p_conv3x3_ex(const p2p_conv3x3_ex_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_conv3x3_ex(*a, (hipStream_t)stream);
+}
+
+int p2p_conv3x3_ex_split(int32_t form, int32_t n, int32_t in_height, int32_t in_width, int32_t c_in, int32_t c_out) {
+  const int rc = conv3x3_check_sizes(form, n, in_height, in_width, c_in, c_out);
+  if (rc < 0) return rc;
+  int oh = 0, ow = 0;
+  conv3x3_out_map(form, in_height, in_width, &oh, &ow);
+  return select_conv3x3(form, n, oh, ow, c_in, c_out).split;
+}
+
+int64_t p2p_conv3x3_ex_workspace_floats(int32_t form, int32_t n, int32_t in_height, int32_t in_width, int32_t c_in,
+                                        int32_t c_out) {
+  const int split = p2p_conv3x3_ex_split(form, n, in_height, in_width, c_in, c_out);
+  if (split < 0) return split;
+  int oh = 0, ow = 0;
+  conv3x3_out_map(form, in_height, in_width, &oh, &ow);
+  return split > 1 ? (int64_t)split * n * oh * ow * c_out : 0;
+}
+
 int p2p_conv3x3_pack(const p2p_conv3x3_pack_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
   return run_conv3x3_pack(*a, (hipStream_t)stream);

@@ -1,7 +1,13 @@
-// conv3x3_kernel: the resnets' 3x3 convolutions (stride 1, padding 1, no bias) as an implicit GEMM
-// on v_mfma_f32_16x16x32_{bf16,f16}.
+// conv3x3_kernel: the U-Net's 3x3 convolutions as an implicit GEMM on v_mfma_f32_16x16x32_{bf16,f16}
+// (DESIGN.md §4.16), in three addressing forms that share everything but where a tap reads:
+//   Same   stride 1, padding 1 (the resnets);
+//   Up2    the padded convolution of the nearest-neighbour 2x upsampling of x, which is never
+//          written: tap (dy, dx) of output pixel (oy, ox) reads low-resolution pixel
+//          ((oy + dy) >> 1, (ox + dx) >> 1) and is valid inside the 2h x 2w map (Upsample2D);
+//   Down2  stride 2, padding 1, even h and w: tap (ky, kx) reads (2 oy + ky - 1, 2 ox + kx - 1) and is
+//          valid where both are >= 0 (Downsample2D).
 //
-//   M = n h w pixels (x is token-major: one pixel's channels are one contiguous K run),
+//   M = n h w output pixels (x is token-major: one pixel's channels are one contiguous K run),
 //   N = c_out, K = 9 c_in walked tap by tap: one K step is one tap and BK channels.
 //
 // A workgroup of four waves (2 x 2) owns a 128-pixel x BN-channel tile (BN = 128 or 160 = 4 or 5
@@ -13,11 +19,14 @@
 // pixel's own, always valid, address and is then replaced by zeros, so no load is conditional and
 // nothing is ever read out of bounds.
 //
-// Epilogue: the f32 accumulators are rounded once; a lane holds four consecutive pixels of one
+// In the Up2 / Down2 forms the source offset of a staged row is no uniform shift of its own: it is
+// worked out per (staged row, tap) when the tap changes, never per channel step.
+//
+// Epilogue: the f32 accumulators, plus the bias where there is one, are rounded once; a lane holds four consecutive pixels of one
 // output channel, the tile is transposed through LDS and stored NCHW in 16-byte pieces along the
 // pixels.  With a K split (small M) every split stores its f32 partial tile in NCHW order into the
-// caller's workspace and conv3x3_reduce_kernel sums the partials in split order: no atomics, the
-// same bits on every launch.
+// caller's workspace and conv3x3_reduce_kernel sums the partials in split order and adds the bias: no
+// atomics, the same bits on every launch.
 #include "p2p_device.h"
 #include "p2p_kernels.h"
 
@@ -34,9 +43,17 @@ struct ConvArgs {
   const uint16_t* x;   // [n, h w, c_in]
   const uint16_t* wp;  // [9, c_out, c_in]
   void* y;             // [n, c_out, h w] 16-bit, or the f32 partials [split][n, c_out, h w]
-  int M, h, w, hw, c_in, c_out;
+  int M, h, w, hw, c_in, c_out;   // h, w: the output map (Same: the input map too)
   int m_tiles, n_tiles, split;
+  const uint16_t* bias;   // [c_out] or null (the split form adds it in the reduce)
+  int ih, iw;             // the input map of the Up2 / Down2 forms
 };
+
+template <bool F16>
+__device__ __forceinline__ float conv_bias(const uint16_t* bias, int co) {
+  if constexpr (F16) return h2f(bias[co]);
+  else return bf2f(bias[co]);
+}
 
 template <bool F16>
 __device__ __forceinline__ f32x4_t mma16(const u32x4_t& a, const u32x4_t& b, const f32x4_t& c) {
@@ -64,14 +81,17 @@ __device__ __forceinline__ int lds_chunk(int r, int c) {
 }
 
 // F16: f16 tensors (else bf16); BK: channels per K step; NF: 16-channel fragments per wave (BN = 32 NF);
-// PARTIAL: store the f32 partial of this block's K range instead of the rounded tile
-template <bool F16, int BK, int NF, bool PARTIAL>
+// PARTIAL: store the f32 partial of this block's K range instead of the rounded tile; FORM: where a tap
+// reads (P2P_CONV_SAME / _UP2 / _DOWN2); BIAS: a.bias is added before the rounding (never with PARTIAL:
+// the reduce adds it) -- compiled in, so that the forms without a bias are the code they were
+template <bool F16, int BK, int NF, bool PARTIAL, int FORM, bool BIAS>
 __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(ConvArgs a) {
   constexpr int BM = kConvBM, BN = 32 * NF;
   constexpr int CPR = BK / 8;                 // 16-byte chunks per staged row
   constexpr int RPP = kConvThreads / CPR;     // rows per staging pass
   constexpr int NA = BM / RPP, NB = BN / RPP;
   static_assert(BM % RPP == 0 && BN % RPP == 0, "staging passes cover the tiles exactly");
+  static_assert(!(PARTIAL && BIAS), "the split form adds the bias in its reduce");
   constexpr int kStage = (BM + BN) * BK * 2;
   constexpr int kEpi = PARTIAL ? 0 : BN * kTilePitch * 2;
   __shared__ __attribute__((aligned(16))) unsigned char lds[kStage > kEpi ? kStage : kEpi];
@@ -94,6 +114,9 @@ __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(ConvArgs a) {
   const int sc = tid % CPR, sr = tid / CPR;
   int a_off[NA], a_yx[NA];     // element offset of the pixel's chunk; (py << 16 | px), or -1 past M
   int a_lds[NA];
+  // Up2 / Down2: a_off is the chunk of the output pixel's own source pixel (the centre tap's, always
+  // valid), a_img the chunk in its image's first pixel, a_src what the current tap reads
+  [[maybe_unused]] int a_img[NA], a_src[NA];
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
     const int r = sr + RPP * i;
@@ -102,7 +125,13 @@ __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(ConvArgs a) {
     m = in ? m : a.M - 1;
     const int rem = m % a.hw;
     const int py = rem / a.w, px = rem - py * a.w;
-    a_off[i] = m * a.c_in + sc * 8;
+    if constexpr (FORM == P2P_CONV_SAME) {
+      a_off[i] = m * a.c_in + sc * 8;
+    } else {
+      a_img[i] = (m / a.hw) * (a.ih * a.iw) * a.c_in + sc * 8;
+      const int own = FORM == P2P_CONV_UP2 ? (py >> 1) * a.iw + (px >> 1) : (2 * py) * a.iw + 2 * px;
+      a_off[i] = a_img[i] + own * a.c_in;
+    }
     a_yx[i] = in ? ((py << 16) | px) : -1;
     a_lds[i] = lds_chunk<BK>(r, sc);
   }
@@ -117,17 +146,44 @@ __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(ConvArgs a) {
 
   u32x4_t ra[NA], rb[NB];
   unsigned ra_ok = 0;          // bit i: ra[i] is inside its image (else write_step stores zeros)
+  [[maybe_unused]] int cur_tap = -1;   // Up2 / Down2: the tap a_src and ra_ok stand for
   auto load_step = [&](int t) {
     const int tap = t / steps_per_tap;
     const int c0 = (t - tap * steps_per_tap) * BK;
     const int ky = tap / 3, dy = ky - 1, dx = tap - ky * 3 - 1;
-    const int shift = (dy * a.w + dx) * a.c_in;
+    if constexpr (FORM == P2P_CONV_SAME) {
+      const int shift = (dy * a.w + dx) * a.c_in;
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int py = a_yx[i] >> 16, px = a_yx[i] & 0xffff;
-      const bool ok = (a_yx[i] >= 0) & ((unsigned)(py + dy) < (unsigned)a.h) & ((unsigned)(px + dx) < (unsigned)a.w);
-      ra[i] = *reinterpret_cast<const u32x4_t*>(a.x + (a_off[i] + c0 + (ok ? shift : 0)));
-      ra_ok = ok ? (ra_ok | (1u << i)) : (ra_ok & ~(1u << i));
+      for (int i = 0; i < NA; ++i) {
+        const int py = a_yx[i] >> 16, px = a_yx[i] & 0xffff;
+        const bool ok = (a_yx[i] >= 0) & ((unsigned)(py + dy) < (unsigned)a.h) & ((unsigned)(px + dx) < (unsigned)a.w);
+        ra[i] = *reinterpret_cast<const u32x4_t*>(a.x + (a_off[i] + c0 + (ok ? shift : 0)));
+        ra_ok = ok ? (ra_ok | (1u << i)) : (ra_ok & ~(1u << i));
+      }
+    } else {
+      if (tap != cur_tap) {   // (uniform) a new tap: where each staged row reads it, and whether it is inside
+        cur_tap = tap;
+        ra_ok = 0;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+          const int py = a_yx[i] >> 16, px = a_yx[i] & 0xffff;
+          bool ok;
+          int src;
+          if constexpr (FORM == P2P_CONV_UP2) {
+            const int ty = py + dy, tx = px + dx;   // in the 2 ih x 2 iw map
+            ok = (a_yx[i] >= 0) & ((unsigned)ty < (unsigned)a.h) & ((unsigned)tx < (unsigned)a.w);
+            src = (ty >> 1) * a.iw + (tx >> 1);
+          } else {
+            const int ty = 2 * py + dy, tx = 2 * px + dx;   // <= ih - 1, iw - 1 for even ih, iw
+            ok = (a_yx[i] >= 0) & (ty >= 0) & (tx >= 0);
+            src = ty * a.iw + tx;
+          }
+          a_src[i] = ok ? a_img[i] + src * a.c_in : a_off[i];
+          ra_ok |= ok ? (1u << i) : 0u;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NA; ++i) ra[i] = *reinterpret_cast<const u32x4_t*>(a.x + (a_src[i] + c0));
     }
     const int wbase = tap * a.c_out * a.c_in + c0;
 #pragma unroll
@@ -192,6 +248,15 @@ __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(ConvArgs a) {
   } else {
     // (the loop's last barrier stands behind every fragment read: the staging image may be reused)
     uint16_t* const tile = reinterpret_cast<uint16_t*>(lds);
+    if constexpr (BIAS) {   // f32 accumulator + bias, then the one rounding
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        const int co = n0 + wn * (16 * NF) + j * 16 + fr;
+        const float b = co < a.c_out ? conv_bias<F16>(a.bias, co) : 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i][j] += b;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -217,15 +282,22 @@ __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(ConvArgs a) {
   }
 }
 
-// y = round(sum over the splits, in split order, of the f32 partials); 8 elements per thread
+// y = round(sum over the splits, in split order, of the f32 partials, + bias[channel] where there is
+// one); 8 elements per thread, all of one channel (hw % 8 == 0)
 template <bool F16>
-__global__ __launch_bounds__(256) void conv3x3_reduce_kernel(const float* ws, uint16_t* y, int64_t total, int split) {
+__global__ __launch_bounds__(256) void conv3x3_reduce_kernel(const float* ws, uint16_t* y, int64_t total, int split,
+                                                             const uint16_t* bias, int hw, int c_out) {
   const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
   if (i >= total) return;
   f32x4_t s0 = *reinterpret_cast<const f32x4_t*>(ws + i), s1 = *reinterpret_cast<const f32x4_t*>(ws + i + 4);
   for (int s = 1; s < split; ++s) {
     s0 += *reinterpret_cast<const f32x4_t*>(ws + s * total + i);
     s1 += *reinterpret_cast<const f32x4_t*>(ws + s * total + i + 4);
+  }
+  if (bias) {
+    const float b = conv_bias<F16>(bias, (int)((unsigned)i / (unsigned)hw % (unsigned)c_out));   // (total < 2^31)
+    s0 += b;
+    s1 += b;
   }
   const u32x4_t o = {pack2<F16>(s0[0], s0[1]), pack2<F16>(s0[2], s0[3]), pack2<F16>(s1[0], s1[1]), pack2<F16>(s1[2], s1[3])};
   *reinterpret_cast<u32x4_t*>(y + i) = o;
@@ -241,47 +313,58 @@ __global__ __launch_bounds__(256) void conv3x3_pack_kernel(const uint16_t* w, ui
   packed[i] = w[r * 9 + tap];
 }
 
-template <bool F16, int BK, int NF>
-void launch_conv_form(const ConvArgs& a, hipStream_t st) {
+template <bool F16, int BK, int NF, int FORM>
+void launch_conv_tile(const ConvArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)(a.m_tiles * a.n_tiles * a.split));
-  if (a.split > 1) launch_kernel((conv3x3_kernel<F16, BK, NF, true>), grid, dim3(kConvThreads), 0, st, a);
-  else launch_kernel((conv3x3_kernel<F16, BK, NF, false>), grid, dim3(kConvThreads), 0, st, a);
+  if (a.split > 1) launch_kernel((conv3x3_kernel<F16, BK, NF, true, FORM, false>), grid, dim3(kConvThreads), 0, st, a);
+  else if (a.bias) launch_kernel((conv3x3_kernel<F16, BK, NF, false, FORM, true>), grid, dim3(kConvThreads), 0, st, a);
+  else launch_kernel((conv3x3_kernel<F16, BK, NF, false, FORM, false>), grid, dim3(kConvThreads), 0, st, a);
+}
+
+template <bool F16, int FORM>
+void launch_conv_form(const ConvArgs& a, const ConvPlan& plan, hipStream_t st) {
+  if (plan.bk == 64 && plan.bn == 160) launch_conv_tile<F16, 64, 5, FORM>(a, st);
+  else if (plan.bk == 64) launch_conv_tile<F16, 64, 4, FORM>(a, st);
+  else launch_conv_tile<F16, 32, 4, FORM>(a, st);
 }
 
 template <bool F16>
-void launch_conv(const ConvArgs& a, const ConvPlan& plan, hipStream_t st) {
-  if (plan.bk == 64 && plan.bn == 160) launch_conv_form<F16, 64, 5>(a, st);
-  else if (plan.bk == 64) launch_conv_form<F16, 64, 4>(a, st);
-  else launch_conv_form<F16, 32, 4>(a, st);
+void launch_conv(const ConvArgs& a, int form, const ConvPlan& plan, hipStream_t st) {
+  if (form == P2P_CONV_UP2) launch_conv_form<F16, P2P_CONV_UP2>(a, plan, st);
+  else if (form == P2P_CONV_DOWN2) launch_conv_form<F16, P2P_CONV_DOWN2>(a, plan, st);
+  else launch_conv_form<F16, P2P_CONV_SAME>(a, plan, st);
 }
 
 bool conv_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-// the launcher: run_conv3x3 (p2p_dispatch.hip) has checked the arguments and chosen the plan
-int launch_conv3x3(const p2p_conv3x3_args& a, const ConvPlan& plan, hipStream_t st) {
+// the launcher: run_conv3x3_ex (p2p_dispatch.hip) has checked the arguments, worked out the output map
+// (out_h x out_w) and chosen the plan
+int launch_conv3x3(const p2p_conv3x3_ex_args& a, int out_h, int out_w, const ConvPlan& plan, hipStream_t st) {
   ConvArgs k;
   k.x = (const uint16_t*)a.x;
   k.wp = (const uint16_t*)a.weight;
-  k.hw = a.height * a.width;
+  k.hw = out_h * out_w;
   k.M = a.n * k.hw;
-  k.h = a.height, k.w = a.width, k.c_in = a.c_in, k.c_out = a.c_out;
+  k.h = out_h, k.w = out_w, k.c_in = a.c_in, k.c_out = a.c_out;
+  k.ih = a.in_height, k.iw = a.in_width;
+  k.bias = plan.split > 1 ? nullptr : (const uint16_t*)a.bias;
   k.m_tiles = (k.M + kConvBM - 1) / kConvBM;
   k.n_tiles = (a.c_out + plan.bn - 1) / plan.bn;
   k.split = plan.split;
   k.y = plan.split > 1 ? (void*)a.workspace : a.y;
-  if (a.dtype == P2P_DTYPE_F16) launch_conv<true>(k, plan, st);
-  else launch_conv<false>(k, plan, st);
+  if (a.dtype == P2P_DTYPE_F16) launch_conv<true>(k, a.form, plan, st);
+  else launch_conv<false>(k, a.form, plan, st);
   if (plan.split > 1) {
     const int64_t total = (int64_t)k.M * a.c_out;   // % 8 == 0 (hw % 8 == 0)
     const dim3 grid((unsigned)((total / 8 + 255) / 256));
     if (a.dtype == P2P_DTYPE_F16)
       launch_kernel(conv3x3_reduce_kernel<true>, grid, dim3(256), 0, st, (const float*)a.workspace, (uint16_t*)a.y, total,
-                    plan.split);
+                    plan.split, (const uint16_t*)a.bias, k.hw, a.c_out);
     else
       launch_kernel(conv3x3_reduce_kernel<false>, grid, dim3(256), 0, st, (const float*)a.workspace, (uint16_t*)a.y, total,
-                    plan.split);
+                    plan.split, (const uint16_t*)a.bias, k.hw, a.c_out);
   }
   return (int)hipGetLastError();
 }

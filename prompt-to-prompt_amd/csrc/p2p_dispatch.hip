@@ -27,17 +27,28 @@ int run_cross(const CrossArgs& a, int io_dtype, int compute, int d, hipStream_t 
   return launch_cross_entry(a, select_precision(io_dtype, compute), d, k, st);
 }
 
-int run_conv3x3(const p2p_conv3x3_args& a, hipStream_t st) {
+int run_conv3x3_ex(const p2p_conv3x3_ex_args& a, hipStream_t st) {
   if (!a.x || !a.weight || !a.y) return P2P_E_ARG;
-  const int rc = conv3x3_check_sizes(a.n, a.height, a.width, a.c_in, a.c_out);
+  const int rc = conv3x3_check_sizes(a.form, a.n, a.in_height, a.in_width, a.c_in, a.c_out);
   if (rc == P2P_E_ARG) return rc;
   if (a.dtype != P2P_DTYPE_BF16 && a.dtype != P2P_DTYPE_F16) return P2P_E_DTYPE;
   if (rc < 0) return rc;
   if (((uintptr_t)a.x | (uintptr_t)a.weight | (uintptr_t)a.y | (uintptr_t)a.workspace) & 15) return P2P_E_ALIGN;
-  const ConvPlan plan = select_conv3x3(a.n, a.height, a.width, a.c_in, a.c_out);
+  if ((uintptr_t)a.bias & 1) return P2P_E_ALIGN;
+  int oh = 0, ow = 0;
+  conv3x3_out_map(a.form, a.in_height, a.in_width, &oh, &ow);   // (checked above)
+  const ConvPlan plan = select_conv3x3(a.form, a.n, oh, ow, a.c_in, a.c_out);
   if (plan.split < 1) return P2P_E_ALIGN;   // a size the selection leaves to the caller's convolution
   if (plan.split > 1 && !a.workspace) return P2P_E_ARG;
-  return launch_conv3x3(a, plan, st);
+  return launch_conv3x3(a, oh, ow, plan, st);
+}
+
+int run_conv3x3(const p2p_conv3x3_args& a, hipStream_t st) {
+  p2p_conv3x3_ex_args e = {};
+  e.x = a.x, e.weight = a.weight, e.y = a.y, e.workspace = a.workspace;
+  e.n = a.n, e.in_height = a.height, e.in_width = a.width, e.c_in = a.c_in, e.c_out = a.c_out;
+  e.dtype = a.dtype, e.form = P2P_CONV_SAME;
+  return run_conv3x3_ex(e, st);
 }
 
 }  // namespace p2p

@@ -213,8 +213,9 @@ int run_bias_residual(const p2p_bias_residual_args& a, hipStream_t st);
 int run_geglu(const p2p_geglu_args& a, hipStream_t st);
 // the resnets' 3x3 convolution: checks and selection (p2p_dispatch.hip), conv3x3_kernel and its
 // reduce launch (p2p_conv.hip), and the once-per-model weight repack
-int run_conv3x3(const p2p_conv3x3_args& a, hipStream_t st);
-int launch_conv3x3(const p2p_conv3x3_args& a, const ConvPlan& plan, hipStream_t st);
+int run_conv3x3(const p2p_conv3x3_args& a, hipStream_t st);   // forwards to run_conv3x3_ex
+int run_conv3x3_ex(const p2p_conv3x3_ex_args& a, hipStream_t st);
+int launch_conv3x3(const p2p_conv3x3_ex_args& a, int out_h, int out_w, const ConvPlan& plan, hipStream_t st);
 int run_conv3x3_pack(const p2p_conv3x3_pack_args& a, hipStream_t st);
 // the glue's backward.  From kGnBwdWideRow pixels a channel's row of the NCHW reduce takes a whole
 // workgroup (four waves), below it one wave; token-major dy leaves one partial per 64-pixel tile.

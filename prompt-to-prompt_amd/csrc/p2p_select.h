@@ -431,4 +431,35 @@ inline int64_t conv3x3_workspace_floats(int n, int h, int w, int c_in, int c_out
   return p.split > 1 ? (int64_t)p.split * n * h * w * c_out : 0;
 }
 
+// The sampling forms (P2P_CONV_*): Up2 reads a map half the output's size, Down2 one twice its size.
+// The output map of a form's input map; false for an unknown form, a size < 1, or an input Down2
+// does not take (odd sizes: its upper edge would be crossed).
+inline bool conv3x3_out_map(int form, int ih, int iw, int* oh, int* ow) {
+  if (ih < 1 || iw < 1 || ih > (1 << 20) || iw > (1 << 20)) return false;
+  switch (form) {
+    case P2P_CONV_SAME: *oh = ih, *ow = iw; return true;
+    case P2P_CONV_UP2: *oh = 2 * ih, *ow = 2 * iw; return true;
+    case P2P_CONV_DOWN2: *oh = ih / 2, *ow = iw / 2; return ih % 2 == 0 && iw % 2 == 0;
+    default: return false;
+  }
+}
+// sizes p2p_conv3x3_ex rejects: conv3x3_check_sizes on the output map, and x's element offsets
+// (Down2's input is four times the output) within 32 bits
+inline int conv3x3_check_sizes(int form, int n, int ih, int iw, int c_in, int c_out) {
+  if (form != P2P_CONV_SAME && form != P2P_CONV_UP2 && form != P2P_CONV_DOWN2) return P2P_E_ARG;
+  if (n < 1 || ih < 1 || iw < 1 || c_in < 1 || c_out < 1) return P2P_E_ARG;
+  if ((int64_t)n * ih * iw > INT32_MAX || (int64_t)n * ih * iw * c_in > INT32_MAX) return P2P_E_ARG;
+  int oh, ow;
+  if (!conv3x3_out_map(form, ih, iw, &oh, &ow)) return P2P_E_ALIGN;
+  return conv3x3_check_sizes(n, oh, ow, c_in, c_out);
+}
+// The plan of a form at its OUTPUT map h x w: tile and split come from the output M exactly as for
+// Same, and Up2 / Down2 are served on the same maps (h w <= kConvMaxHW, h w % 8 == 0).  Which of the
+// U-Net's six resampling convolutions take the kernel was measured per shape (tools/conv_bench.py,
+// DESIGN.md §4.16).
+inline ConvPlan select_conv3x3(int form, int n, int h, int w, int c_in, int c_out) {
+  if (form != P2P_CONV_SAME && form != P2P_CONV_UP2 && form != P2P_CONV_DOWN2) return ConvPlan{0, 0, 0};
+  return select_conv3x3(n, h, w, c_in, c_out);
+}
+
 }  // namespace p2p

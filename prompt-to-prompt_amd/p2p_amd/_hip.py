@@ -180,6 +180,15 @@ class Conv3x3Args(ctypes.Structure):
     ]
 
 
+class Conv3x3ExArgs(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("n", ctypes.c_int32), ("in_height", ctypes.c_int32), ("in_width", ctypes.c_int32), ("c_in", ctypes.c_int32),
+        ("c_out", ctypes.c_int32), ("dtype", ctypes.c_int32), ("form", ctypes.c_int32),
+    ]
+
+
 class Conv3x3PackArgs(ctypes.Structure):
     _fields_ = [
         ("weight", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("c_in", ctypes.c_int32), ("c_out", ctypes.c_int32),
@@ -325,7 +334,8 @@ def lib():
                  "p2p_mutual_attn_kernel": ctypes.c_char_p,
                  "p2p_attn_bwd_workspace": ctypes.c_int64, "p2p_group_norm_stats_floats": ctypes.c_int64,
                  "p2p_group_norm_bwd_workspace_floats": ctypes.c_int64,
-                 "p2p_conv3x3_workspace_floats": ctypes.c_int64}
+                 "p2p_conv3x3_workspace_floats": ctypes.c_int64,
+                 "p2p_conv3x3_ex_workspace_floats": ctypes.c_int64}
         for fn in EXPORTED_SYMBOLS:
             getattr(L, fn).restype = other.get(fn, ctypes.c_int)
         L.p2p_error_string.argtypes = [ctypes.c_int]
@@ -358,6 +368,9 @@ def lib():
         L.p2p_conv3x3_split.argtypes = [i32, i32, i32, i32, i32]
         L.p2p_conv3x3_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
         L.p2p_conv3x3_pack.argtypes = [ctypes.POINTER(Conv3x3PackArgs), vp]
+        L.p2p_conv3x3_ex.argtypes = [ctypes.POINTER(Conv3x3ExArgs), vp]
+        L.p2p_conv3x3_ex_split.argtypes = [i32, i32, i32, i32, i32, i32]
+        L.p2p_conv3x3_ex_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32]
         L.p2p_group_norm_bwd.argtypes = [ctypes.POINTER(GroupNormBwdArgs), vp]
         L.p2p_group_norm_bwd_workspace_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_geglu_bwd.argtypes = [ctypes.POINTER(GegluBwdArgs), vp]
@@ -410,7 +423,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_time_proj", "p2p_conv3x3", "p2p_conv3x3_split", "p2p_conv3x3_workspace_floats",
                     "p2p_conv3x3_pack", "p2p_dpm_step", "p2p_direct_step", "p2p_direct_offset",
                     "p2p_ddpm_step", "p2p_ddpm_noise", "p2p_mutual_attn_fwd", "p2p_mutual_attn_kernel",
-                    "p2p_token_classes")
+                    "p2p_token_classes", "p2p_conv3x3_ex", "p2p_conv3x3_ex_split",
+                    "p2p_conv3x3_ex_workspace_floats")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -1229,6 +1243,78 @@ def conv3x3(x_tokens: torch.Tensor, packed: torch.Tensor, h: int, w: int):
     a.n, a.height, a.width, a.c_in, a.c_out = N, h, w, c_in, c_out
     a.dtype = _glue_dtype(x_tokens)
     return y if _glue_rc(lib().p2p_conv3x3(ctypes.byref(a), _stream(x_tokens.device)), "p2p_conv3x3") else None
+
+
+# the sampling forms of p2p_conv3x3_ex (include/p2p_hip.h)
+CONV_SAME, CONV_UP2, CONV_DOWN2 = 0, 1, 2
+
+
+def conv3x3_out_map(form: int, h: int, w: int):
+    """The output map of a form's input map h x w."""
+    return {CONV_SAME: (h, w), CONV_UP2: (2 * h, 2 * w), CONV_DOWN2: (h // 2, w // 2)}[form]
+
+
+def conv3x3_ex_split(form: int, n: int, h: int, w: int, c_in: int, c_out: int) -> int:
+    """conv3x3_split for a sampling form, from the INPUT map h x w: 0 or negative = not served."""
+    return int(lib().p2p_conv3x3_ex_split(form, n, h, w, c_in, c_out))
+
+
+def conv3x3_ex(x_tokens: torch.Tensor, packed: torch.Tensor, bias, h: int, w: int, form: int = CONV_SAME):
+    """The 3x3 convolution of the token-major x_tokens [N, h*w, C_in] in a sampling form
+    (p2p_conv3x3_ex), with ``bias`` ([C_out] or None) added before the one rounding, as [N, C_out, H', W']:
+    CONV_SAME F.conv2d(x, weight, bias, 1, 1); CONV_UP2 the same of F.interpolate(x, scale_factor=2,
+    mode="nearest"), which is never written; CONV_DOWN2 F.conv2d(x, weight, bias, 2, 1) for even h, w.
+    None where the library does not serve the operands; the caller runs its own lines."""
+    _require_cuda(x_tokens, packed, bias)
+    if x_tokens.dim() != 3 or packed.dim() != 3 or not x_tokens.is_contiguous() or not packed.is_contiguous() or \
+            packed.dtype != x_tokens.dtype:
+        return None
+    N, HW, c_in = x_tokens.shape
+    c_out = packed.shape[1]
+    if HW != h * w or packed.shape[0] != 9 or packed.shape[2] != c_in or form not in (CONV_SAME, CONV_UP2, CONV_DOWN2):
+        raise HipError(f"conv3x3_ex: x {tuple(x_tokens.shape)} / weight {tuple(packed.shape)} / {h} x {w} / form {form} "
+                       f"do not match")
+    n_ws = int(lib().p2p_conv3x3_ex_workspace_floats(form, N, h, w, c_in, c_out))
+    if n_ws < 0 or conv3x3_ex_split(form, N, h, w, c_in, c_out) < 1:
+        return None
+    a = Conv3x3ExArgs()
+    y = x_tokens.new_empty((N, c_out, *conv3x3_out_map(form, h, w)))
+    a.x, a.weight, a.y = x_tokens.data_ptr(), packed.data_ptr(), y.data_ptr()
+    if bias is not None:
+        a.bias = _vec(bias, x_tokens, c_out).data_ptr()
+    if n_ws:
+        ws = torch.empty(n_ws, dtype=torch.float32, device=x_tokens.device)
+        a.workspace = ws.data_ptr()
+    a.n, a.in_height, a.in_width, a.c_in, a.c_out = N, h, w, c_in, c_out
+    a.dtype, a.form = _glue_dtype(x_tokens), form
+    return y if _glue_rc(lib().p2p_conv3x3_ex(ctypes.byref(a), _stream(x_tokens.device)), "p2p_conv3x3_ex") else None
+
+
+def conv_input_tokens(x):
+    """The token-major copy [N, H*W, C] of a dense NCHW activation that has no norm in front of its
+    convolution (Upsample2D, Downsample2D): one p2p_nchw_to_tokens launch on the forward path, under
+    the forward bindings' contract -- None where the kernel does not serve x (``nchw_to_tokens`` is
+    the backward's binding of the same kernel, and raises)."""
+    _require_cuda(x)
+    if x.dim() != 4 or not x.is_contiguous():
+        return None
+    N, C, H, W = x.shape
+    t = NchwToTokensArgs()
+    dst = x.new_empty((N, H * W, C))
+    t.src, t.dst = x.data_ptr(), dst.data_ptr()
+    t.n, t.channels, t.hw = N, C, H * W
+    t.dtype = _glue_dtype(x)
+    return dst if _glue_rc(lib().p2p_nchw_to_tokens(ctypes.byref(t), _stream(x.device)), "p2p_nchw_to_tokens") else None
+
+
+def conv3x3_up2(x_tokens, packed, bias, h: int, w: int):
+    """conv3x3_ex in the CONV_UP2 form: Upsample2D's interpolate + convolution from the low-resolution map."""
+    return conv3x3_ex(x_tokens, packed, bias, h, w, CONV_UP2)
+
+
+def conv3x3_down2(x_tokens, packed, bias, h: int, w: int):
+    """conv3x3_ex in the CONV_DOWN2 form: Downsample2D's stride-2 convolution."""
+    return conv3x3_ex(x_tokens, packed, bias, h, w, CONV_DOWN2)
 
 
 def geglu(x):

@@ -312,21 +312,53 @@ class ResnetBlock2D(nn.Module):
         return x + h
 
 
+def _resample_conv(conv: nn.Conv2d, x, form: int):
+    """``conv`` of x [N, C, H, W] in a sampling form of conv3x3_kernel (Up2: of x's nearest 2x upsampling,
+    which is never written; Down2: at stride 2), bias included: one p2p_nchw_to_tokens pass over x (``_hip.conv_input_tokens``) and
+    the kernel.  None where the module runs its own lines: the conditions of the resnets'
+    convolutions (``fused_glue`` or ``fused_glue_grad``, CONV_HIP, a shape the selection serves, a
+    packed weight -- none on a cache miss under graph capture)."""
+    if not CONV_HIP or x.dim() != 4:
+        return None
+    if not (fused_glue(x, conv.weight) or fused_glue_grad(x, params=(conv.weight, conv.bias), tokens=True)):
+        return None
+    N, C, H, W = x.shape
+    if (H * W) % 8 or C % 8 or not x.is_contiguous() or \
+            _hip.conv3x3_ex_split(form, N, H, W, conv.in_channels, conv.out_channels) < 1:
+        return None
+    packed = _hip.CONV_WEIGHTS.get(conv)
+    if packed is None:
+        return None
+    return unet_grad.resample_conv3x3(x, packed, conv.weight, conv.bias, form)
+
+
 class Downsample2D(nn.Module):
-    def __init__(self, ch):
+    def __init__(self, ch, conv_hip: bool = False):
         super().__init__()
         self.conv = nn.Conv2d(ch, ch, 3, stride=2, padding=1)
+        # conv3x3_kernel's Down2 form was measured on the U-Net's shapes only: the blocks below opt in
+        self._conv_hip = conv_hip
 
     def forward(self, x):
+        if self._conv_hip:
+            y = _resample_conv(self.conv, x, _hip.CONV_DOWN2)
+            if y is not None:
+                return y
         return self.conv(x)
 
 
 class Upsample2D(nn.Module):
-    def __init__(self, ch):
+    def __init__(self, ch, conv_hip: bool = False):
         super().__init__()
         self.conv = nn.Conv2d(ch, ch, 3, padding=1)
+        # as Downsample2D: the U-Net's blocks opt in, the VAE (vae.py) keeps MIOpen
+        self._conv_hip = conv_hip
 
     def forward(self, x):
+        if self._conv_hip:
+            y = _resample_conv(self.conv, x, _hip.CONV_UP2)
+            if y is not None:
+                return y
         return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
 
 
@@ -337,7 +369,7 @@ class CrossAttnDownBlock2D(nn.Module):
                                       for i in range(layers)])
         self.attentions = nn.ModuleList([Transformer2DModel(heads, out_ch // heads, out_ch, context_dim)
                                          for _ in range(layers)])
-        self.downsamplers = nn.ModuleList([Downsample2D(out_ch)]) if downsample else None
+        self.downsamplers = nn.ModuleList([Downsample2D(out_ch, conv_hip=True)]) if downsample else None
 
     def forward(self, x, temb, ctx):
         outs = ()
@@ -355,7 +387,7 @@ class DownBlock2D(nn.Module):
         super().__init__()
         self.resnets = nn.ModuleList([ResnetBlock2D(in_ch if i == 0 else out_ch, out_ch, temb_ch)
                                       for i in range(layers)])
-        self.downsamplers = nn.ModuleList([Downsample2D(out_ch)]) if downsample else None
+        self.downsamplers = nn.ModuleList([Downsample2D(out_ch, conv_hip=True)]) if downsample else None
 
     def forward(self, x, temb, ctx=None):
         outs = ()
@@ -381,7 +413,7 @@ class UpBlock2D(nn.Module):
     def __init__(self, in_ch, prev_ch, out_ch, layers=3, upsample=True, temb_ch=1280):
         super().__init__()
         self.resnets = _up_resnets(in_ch, prev_ch, out_ch, layers, temb_ch)
-        self.upsamplers = nn.ModuleList([Upsample2D(out_ch)]) if upsample else None
+        self.upsamplers = nn.ModuleList([Upsample2D(out_ch, conv_hip=True)]) if upsample else None
 
     def forward(self, x, temb, skips, ctx=None):
         for res in self.resnets:
@@ -398,7 +430,7 @@ class CrossAttnUpBlock2D(nn.Module):
         self.resnets = _up_resnets(in_ch, prev_ch, out_ch, layers, temb_ch)
         self.attentions = nn.ModuleList([Transformer2DModel(heads, out_ch // heads, out_ch, context_dim)
                                          for _ in range(layers)])
-        self.upsamplers = nn.ModuleList([Upsample2D(out_ch)]) if upsample else None
+        self.upsamplers = nn.ModuleList([Upsample2D(out_ch, conv_hip=True)]) if upsample else None
 
     def forward(self, x, temb, skips, ctx=None):
         for res, att in zip(self.resnets, self.attentions):

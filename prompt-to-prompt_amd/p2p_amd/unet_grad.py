@@ -15,7 +15,10 @@ F.layer_norm at the saved sum.
 The 3x3 convolution (csrc/p2p_conv.hip) has no HIP backward either: ``_GroupNormConv3x3`` runs the
 token-major p2p_group_norm and p2p_conv3x3 forward -- the bits of the no-grad forward again -- and
 takes torch's own input gradient of the convolution from the weight and dy into p2p_group_norm_bwd;
-the convolution's input is not saved.
+the convolution's input is not saved.  ``_ResampleConv3x3`` does the same for Upsample2D's and
+Downsample2D's convolutions (the kernel's Up2 / Down2 forms on a token-major copy of the input): the
+no-grad forward's two launches, then torch's input gradient of the convolution and, for Up2, of the
+nearest upsampling.
 
 The wrappers return None where the forward binding reports the input unsupported, as the bindings
 do; a backward binding that rejects what its forward served raises ``HipError``.
@@ -177,6 +180,51 @@ def group_norm_conv3x3(x, gamma, beta, groups: int, eps: float, packed, weight, 
             _hip.conv3x3_split(x.shape[0], x.shape[2], x.shape[3], x.shape[1], packed.shape[1]) < 1:
         return None
     return _GroupNormConv3x3.apply(x, gamma, beta, chan_add, chan_bias, int(groups), float(eps), packed, weight)
+
+
+class _ResampleConv3x3(torch.autograd.Function):
+    """Upsample2D's / Downsample2D's convolution on p2p_nchw_to_tokens (``_hip.conv_input_tokens``) and p2p_conv3x3_ex (the Up2 or
+    Down2 form, with the bias): the two launches and the bits of the no-grad forward.  Backward:
+    torch's input gradient of the convolution (aten.convolution_backward with only the input mask
+    set, from the weight and dy) at stride 2 for Down2; for Up2 at stride 1 on the upsampled map,
+    followed by the nearest upsampling's backward.  The convolution's input is not saved (its shape
+    is); weight and bias get no gradient (fused_glue_grad declines parameters that require one)."""
+
+    @staticmethod
+    def forward(ctx, x, packed, weight, bias, form):
+        tokens = _hip.conv_input_tokens(x)
+        y = None if tokens is None else _hip.conv3x3_ex(tokens, packed, bias, x.shape[2], x.shape[3], form)
+        if y is None:
+            raise _hip.HipError(f"resampling conv3x3 under autograd: {tuple(x.shape)} {x.dtype} is not served")
+        ctx.save_for_backward(weight)
+        ctx.form, ctx.x_shape = form, tuple(x.shape)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        weight, = ctx.saved_tensors
+        n, c, h, w = ctx.x_shape
+        if ctx.form == _hip.CONV_DOWN2:
+            dx = torch.nn.grad.conv2d_input((n, c, h, w), weight, dy.contiguous(), stride=2, padding=1)
+        else:
+            du = torch.nn.grad.conv2d_input((n, c, 2 * h, 2 * w), weight, dy.contiguous(), stride=1, padding=1)
+            dx = torch.ops.aten.upsample_nearest2d_backward(du, [2 * h, 2 * w], [n, c, h, w], 2.0, 2.0)
+        return dx, None, None, None, None
+
+
+def resample_conv3x3(x, packed, weight, bias, form: int):
+    """_hip.conv3x3_ex of the token-major copy of x [N, C, H, W] in the Up2 or Down2 form,
+    differentiable with respect to x; ``weight`` is the [C_out, C_in, 3, 3] tensor ``packed`` was made
+    from.  None where a binding does not serve the operands."""
+    n, c, h, w = x.shape
+    if not _dense16(x) or packed.dtype != x.dtype or (h * w) % 8 or c % 8 or \
+            _hip.conv3x3_ex_split(form, n, h, w, c, packed.shape[1]) < 1:
+        return None
+    if not x.requires_grad:
+        tokens = _hip.conv_input_tokens(x)
+        return None if tokens is None else _hip.conv3x3_ex(tokens, packed, bias, h, w, form)
+    return _ResampleConv3x3.apply(x, packed, weight, bias, form)
 
 
 def geglu(x):

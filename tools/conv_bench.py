@@ -7,9 +7,18 @@ is captured into a HIP graph of --reps calls that rotate over enough operand set
 line per shape: microseconds per call (median of --iters replays), the kernel's TFLOP/s and its
 fraction of the 2500 TFLOP/s dense 16-bit peak, and the selection's K split.
 
-    python tools/conv_bench.py [--iters 15] [--reps 32] [--dtype bf16|f16] [--n 8]
+Then the six resampling convolutions (Upsample2D, Downsample2D) in the same method: what the module
+launched before (F.interpolate + MIOpen's convolution with its bias, or the stride-2 convolution with
+its bias, and everything MIOpen adds) against p2p_nchw_to_tokens on the low-resolution map +
+p2p_conv3x3_ex in the Up2 / Down2 form with the bias.  --repeat R measures every chain R times: the
+spread between the medians of one row is the bar a difference has to clear.  --other-lib runs the
+resnet rows' p2p_conv3x3 on another build of the library too (the parent commit's) in the same call.
+
+    python tools/conv_bench.py [--iters 15] [--reps 32] [--dtype bf16|f16] [--n 8] [--repeat 1]
+                               [--other-lib /path/to/libp2p_hip.so] [--only resnet|resample]
 """
 import argparse
+import ctypes
 import math
 import os
 import sys
@@ -30,6 +39,9 @@ SHAPES = [(64, 320, 320, 7), (64, 640, 320, 2), (64, 960, 320, 1),
           (32, 320, 640, 1), (32, 640, 640, 6), (32, 960, 640, 1), (32, 1280, 640, 1), (32, 1920, 640, 1),
           (16, 640, 1280, 1), (16, 1280, 1280, 6), (16, 1920, 1280, 1), (16, 2560, 1280, 2),
           (8, 1280, 1280, 11), (8, 2560, 1280, 3)]
+# (form, input H = W, channels): the U-Net's three Upsample2D and three Downsample2D convolutions
+RESAMPLE = [("up2", 8, 1280), ("up2", 16, 1280), ("up2", 32, 640),
+            ("down2", 64, 320), ("down2", 32, 640), ("down2", 16, 1280)]
 
 
 def graph_us(fn, sets, reps, iters, dev):
@@ -62,6 +74,9 @@ def main():
     ap.add_argument("--reps", type=int, default=32)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     ap.add_argument("--n", type=int, default=8)
+    ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--other-lib")
+    ap.add_argument("--only", choices=["resnet", "resample"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("conv_bench needs a GPU")
@@ -75,8 +90,14 @@ def main():
     print("us per call: [before] NCHW norm + MIOpen conv | MIOpen conv alone || [now] token norm + p2p_conv3x3 | "
           "p2p_conv3x3 alone")
     saved = 0.0
+    other = None
+    if args.other_lib:
+        other = ctypes.CDLL(args.other_lib)
+        other.p2p_conv3x3.argtypes = [ctypes.POINTER(_hip.Conv3x3Args), ctypes.c_void_p]
+        other.p2p_conv3x3_workspace_floats.restype = ctypes.c_int64
+        other.p2p_conv3x3_workspace_floats.argtypes = [ctypes.c_int32] * 5
     with torch.no_grad():
-        for res, cin, cout, count in SHAPES:
+        for res, cin, cout, count in ([] if args.only == "resample" else SHAPES):
             split = _hip.conv3x3_split(N, res, res, cin, cout)
             per_set = N * res * res * (2 * cin + cout) * 2 + 2 * 9 * cin * cout * 2
             sets = min(16, max(2, math.ceil(600e6 / per_set)))
@@ -99,6 +120,20 @@ def main():
             def ours(i):
                 return _hip.conv3x3(toks[i], packed[i], res, res)
 
+            def theirs(i):   # p2p_conv3x3 of the other build on the same operands
+                a = _hip.Conv3x3Args()
+                y = toks[i].new_empty((N, cout, res, res))
+                a.x, a.weight, a.y = toks[i].data_ptr(), packed[i].data_ptr(), y.data_ptr()
+                n_ws = other.p2p_conv3x3_workspace_floats(N, res, res, cin, cout)
+                if n_ws:
+                    ws_ = torch.empty(n_ws, dtype=torch.float32, device=dev)
+                    a.workspace = ws_.data_ptr()
+                a.n, a.height, a.width, a.c_in, a.c_out = N, res, res, cin, cout
+                a.dtype = _hip._glue_dtype(toks[i])
+                rc = other.p2p_conv3x3(ctypes.byref(a), _hip._stream(dev))
+                assert rc == 0, rc
+                return y
+
             variants = [before, miopen] + ([now, ours] if split >= 1 else [])
             us = [graph_us(fn, sets, args.reps, args.iters, dev) for fn in variants]
             gflop = 2.0 * N * res * res * 9 * cin * cout / 1e9
@@ -111,9 +146,62 @@ def main():
                 saved += count * (us[0] - us[2])
             else:
                 line += " || not served by the selection"
+            if other is not None and split >= 1:
+                pairs = [(graph_us(ours, sets, args.reps, args.iters, dev), graph_us(theirs, sets, args.reps, args.iters, dev))
+                         for _ in range(max(2, args.repeat))]
+                line += ("  alone, this build / other build, repeated: " +
+                         ", ".join(f"{a:.1f} / {b:.1f}" for a, b in pairs))
             print(line, flush=True)
             del xs, ws, nchw, toks, packed
-    print(f"sum over the served convolutions of a U-Net call: {saved / 1e3:.2f} ms less per call")
+    if args.only != "resample":
+        print(f"sum over the served convolutions of a U-Net call: {saved / 1e3:.2f} ms less per call")
+    if args.only == "resnet":
+        return
+
+    print("the resampling convolutions, us per call: [before] F.interpolate + MIOpen conv + bias (down2: the stride-2 conv + "
+          "bias) || [now] p2p_nchw_to_tokens + p2p_conv3x3_ex with the bias | p2p_conv3x3_ex alone")
+    gained = 0.0
+    with torch.no_grad():
+        for form, res, ch in RESAMPLE:
+            up = form == "up2"
+            code = _hip.CONV_UP2 if up else _hip.CONV_DOWN2
+            out = 2 * res if up else res // 2
+            split = _hip.conv3x3_ex_split(code, N, res, res, ch, ch)
+            per_set = N * (res * res + out * out) * ch * 2 * 2 + 2 * 9 * ch * ch * 2
+            sets = min(16, max(2, math.ceil(600e6 / per_set)))
+            xs = [torch.randn(N, ch, res, res, device=dev, generator=g).to(dtype) for _ in range(sets)]
+            ws = [(torch.randn(ch, ch, 3, 3, device=dev, generator=g) / math.sqrt(9 * ch)).to(dtype) for _ in range(sets)]
+            bs = [torch.randn(ch, device=dev, generator=g).to(dtype) for _ in range(sets)]
+            toks = [_hip.nchw_to_tokens(x) for x in xs]
+            packed = [_hip.conv3x3_pack(w) for w in ws]
+
+            def before(i):
+                if up:
+                    return F.conv2d(F.interpolate(xs[i], scale_factor=2.0, mode="nearest"), ws[i], bs[i], 1, 1)
+                return F.conv2d(xs[i], ws[i], bs[i], 2, 1)
+
+            def now(i):
+                return _hip.conv3x3_ex(_hip.conv_input_tokens(xs[i]), packed[i], bs[i], res, res, code)
+
+            def ours(i):
+                return _hip.conv3x3_ex(toks[i], packed[i], bs[i], res, res, code)
+
+            gflop = 2.0 * N * out * out * 9 * ch * ch / 1e9
+            b_us = [graph_us(before, sets, args.reps, args.iters, dev) for _ in range(args.repeat)]
+            line = f"  {form:5s} {res:2d}^2 -> {out:2d}^2 {ch:4d} -> {ch:4d} {gflop:6.1f} GFLOP  before " + \
+                " ".join(f"{u:7.1f}" for u in b_us)
+            if split >= 1:
+                n_us = [graph_us(now, sets, args.reps, args.iters, dev) for _ in range(args.repeat)]
+                o_us = graph_us(ours, sets, args.reps, args.iters, dev)
+                tf = gflop / o_us * 1e3
+                line += (" || now " + " ".join(f"{u:7.1f}" for u in n_us) + f" | {o_us:7.1f} ({tf:5.0f} TF)  split {split}  "
+                         f"chain {sorted(b_us)[len(b_us) // 2] / sorted(n_us)[len(n_us) // 2]:.2f}x")
+                gained += sorted(b_us)[len(b_us) // 2] - sorted(n_us)[len(n_us) // 2]
+            else:
+                line += " || not served by the selection"
+            print(line, flush=True)
+            del xs, ws, bs, toks, packed
+    print(f"sum over the served resampling convolutions of a U-Net call: {gained / 1e3:.3f} ms less per call")
 
 
 if __name__ == "__main__":

@@ -5,7 +5,10 @@ With --split-last N: the dominant hot-path kernel's launches split in dispatch o
 (bench.py's eager per-launch timing pass after a graphed timed region) against the rest (warm-up and
 graph replays) --, each without the launches that ran beside a clock probe (bench.py's ClockProbe:
 those lose 8 CUs and leave the bench's averages too).
-Usage: python tools/rocpd_summary.py <run_results.db> [--split-last N] [> summary.txt]"""
+With --rows REGEX: every kernel whose name matches, by launch grid, with its calls, total and average
+-- the rows of a before / after comparison that the top 15 do not reach.
+Usage: python tools/rocpd_summary.py <run_results.db> [--split-last N] [--rows REGEX] [> summary.txt]"""
+import re
 import sqlite3
 import sys
 
@@ -38,7 +41,20 @@ def split_last(c, n_last):
         print(f"  {label:40s} avg {a:8.2f} us over {n} launches ({p} beside a clock probe left out)")
 
 
-def main(path, n_last=0):
+def matching_rows(rows, pattern):
+    rx = re.compile(pattern)
+    grp = {}
+    for name, dur, gx, wx, vg, lds in rows:
+        if rx.search(name):
+            short = name.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
+            grp.setdefault((short, gx // wx if wx else gx), []).append(dur)
+    print(f"\n== kernels matching /{pattern}/, by grid")
+    for (short, nwg), ds in sorted(grp.items(), key=lambda kv: -sum(kv[1])):
+        print(f"calls {len(ds):6d}  total {sum(ds) / 1e6:9.3f} ms  avg {sum(ds) / len(ds) / 1e3:9.2f} us  wgs {nwg:6d}  {short[:120]}")
+    print(f"total of the matching kernels: {sum(sum(ds) for ds in grp.values()) / 1e6:.3f} ms")
+
+
+def main(path, n_last=0, pattern=None):
     c = sqlite3.connect(path)
     rows = c.execute("select name, duration, grid_x, workgroup_x, vgpr_count, lds_size from kernels").fetchall()
     tot = sum(r[1] for r in rows)
@@ -61,6 +77,8 @@ def main(path, n_last=0):
               f"wgs {nwg:6d} x {wx:4d} thr  vgpr {vg:3d}  lds {lds:6d}  {short[:100]}")
 
 
+    if pattern:
+        matching_rows(rows, pattern)
     if n_last:
         split_last(c, n_last)
 
@@ -72,4 +90,9 @@ if __name__ == "__main__":
         i = args.index("--split-last")
         n = int(args[i + 1])
         del args[i:i + 2]
-    main(args[0], n)
+    pattern = None
+    if "--rows" in args:
+        i = args.index("--rows")
+        pattern = args[i + 1]
+        del args[i:i + 2]
+    main(args[0], n, pattern)
