@@ -677,6 +677,49 @@ typedef struct {
 
 int p2p_conv3x3_pack(const p2p_conv3x3_pack_args* a, p2p_stream_t stream);
 
+/* p2p_linear: y = epilogue(x[m, k] . weight[n, k]^T), the transformer blocks' feed-forward GEMMs on
+ * the tile loop of p2p_conv3x3 (additive to ABI 16), under the glue's contract: 16-bit tensors, f32
+ * accumulation, ONE rounding per output, no atomics, the same bits on every launch.  x is token-major
+ * with a row stride in elements (% 8 == 0, >= k); weight is nn.Linear's own dense weight; y is dense.
+ *   P2P_LINEAR_BIAS      y[m, j] = acc + bias[j];
+ *   P2P_LINEAR_GEGLU     weight is [2 n, k], bias [2 n]: y[m, j] = (acc[m, j] + bias[j]) *
+ *                        gelu(acc[m, n + j] + bias[n + j]), j < n, gelu the exact erf form in f32.
+ *                        p_out (nullable): [m, 2 n] dense, the rounded pre-activation acc + bias;
+ *                        asking for it does not change y's bits;
+ *   P2P_LINEAR_RESIDUAL  y[m, j] = acc + bias[j] + res[m, j], res token-major with a row stride
+ *                        (% 8 == 0, >= n).
+ * bias is nullable in every form.  Small m splits k over several workgroups per tile (never the
+ * GEGLU form); their f32 partials go through `workspace` and a second launch sums them in split
+ * order and adds bias and residual.
+ * Rejected before any launch: a null x / weight / y (res in the RESIDUAL form), an unknown form, a
+ * size < 1, an element offset of x, weight, y, res or p_out beyond int32, a null workspace where the
+ * sizes need one (P2P_E_ARG); f32 (P2P_E_DTYPE); k % 32, n % 8, a row stride % 8 or shorter than its
+ * row, a pointer off 16 bytes (bias: 2), and sizes p2p_linear_split answers 0 for (P2P_E_ALIGN: the
+ * caller runs its own GEMM). */
+enum { P2P_LINEAR_BIAS = 0, P2P_LINEAR_GEGLU = 1, P2P_LINEAR_RESIDUAL = 2 };
+
+typedef struct {
+  const void* x;        /* [m, k], rows x_row_stride apart                                      */
+  const void* weight;   /* [n, k] dense; P2P_LINEAR_GEGLU: [2 n, k]                             */
+  const void* bias;     /* [n] ([2 n]) or NULL                                                  */
+  const void* res;      /* P2P_LINEAR_RESIDUAL: [m, n], rows res_row_stride apart; else unused  */
+  void* y;              /* [m, n] dense                                                         */
+  void* p_out;          /* P2P_LINEAR_GEGLU: [m, 2 n] dense or NULL; else unused                */
+  float* workspace;     /* p2p_linear_workspace_floats() f32; may be NULL where that is 0       */
+  int64_t x_row_stride, res_row_stride;
+  int32_t m, k, n;      /* n: output columns                                                    */
+  int32_t form;         /* P2P_LINEAR_*                                                         */
+  int32_t dtype;        /* P2P_DTYPE_BF16 / P2P_DTYPE_F16: every tensor but workspace           */
+} p2p_linear_args;
+
+int p2p_linear(const p2p_linear_args* a, p2p_stream_t stream);
+/* Workgroups along k per output tile for these sizes (a function of the sizes only): 1 = one launch,
+ * > 1 = the split form with its reduce launch, 0 = not served (a shape measured slower than the GEMM
+ * it would replace), or the P2P_E_* code p2p_linear answers for the sizes. */
+int p2p_linear_split(int32_t form, int32_t m, int32_t k, int32_t n);
+/* f32 elements p2p_linear needs behind `workspace` (0 without a split), or the P2P_E_* code. */
+int64_t p2p_linear_workspace_floats(int32_t form, int32_t m, int32_t k, int32_t n);
+
 /* GEGLU: out[m, j] = in[m, j] * gelu(in[m, d + j]), j < d, gelu the exact erf form (F.gelu's
  * default).  Row strides in elements, multiples of 8 (as d), in_row_stride >= 2 d. */
 typedef struct {

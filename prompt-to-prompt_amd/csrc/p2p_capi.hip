@@ -550,6 +550,21 @@ int p2p_conv3x3_pack(const p2p_conv3x3_pack_args* a, p2p_stream_t stream) {
   return run_conv3x3_pack(*a, (hipStream_t)stream);
 }
 
+int p2p_linear(const p2p_linear_args* a, p2p_stream_t stream) {
+  if (!a) return P2P_E_ARG;
+  return run_linear(*a, (hipStream_t)stream);
+}
+
+int p2p_linear_split(int32_t form, int32_t m, int32_t k, int32_t n) {
+  const int rc = linear_check_sizes(form, m, k, n);
+  return rc < 0 ? rc : select_linear(form, m, k, n).split;
+}
+
+int64_t p2p_linear_workspace_floats(int32_t form, int32_t m, int32_t k, int32_t n) {
+  const int rc = linear_check_sizes(form, m, k, n);
+  return rc < 0 ? rc : linear_workspace_floats(form, m, k, n);
+}
+
 int p2p_geglu(const p2p_geglu_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
   return run_geglu(*a, (hipStream_t)stream);

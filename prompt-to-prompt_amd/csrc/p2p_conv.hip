@@ -27,16 +27,14 @@
 // pixels.  With a K split (small M) every split stores its f32 partial tile in NCHW order into the
 // caller's workspace and conv3x3_reduce_kernel sums the partials in split order and adds the bias: no
 // atomics, the same bits on every launch.
-#include "p2p_device.h"
-#include "p2p_kernels.h"
+//
+// The tile loop itself (staging image, swizzle, MFMAs, barriers) is p2p_mma_tile.h's, shared with
+// linear_kernel (p2p_linear.hip).
+#include "p2p_mma_tile.h"
 
 namespace p2p {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
-
-constexpr int kConvThreads = 256;
 constexpr int kTilePitch = kConvBM + 8;   // 16-bit elements per channel row of the epilogue's transposed tile
 
 struct ConvArgs {
@@ -48,37 +46,6 @@ struct ConvArgs {
   const uint16_t* bias;   // [c_out] or null (the split form adds it in the reduce)
   int ih, iw;             // the input map of the Up2 / Down2 forms
 };
-
-template <bool F16>
-__device__ __forceinline__ float conv_bias(const uint16_t* bias, int co) {
-  if constexpr (F16) return h2f(bias[co]);
-  else return bf2f(bias[co]);
-}
-
-template <bool F16>
-__device__ __forceinline__ f32x4_t mma16(const u32x4_t& a, const u32x4_t& b, const f32x4_t& c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0,
-                                                   0);
-}
-
-template <bool F16>
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  if constexpr (F16) return (uint32_t)f2h(lo) | ((uint32_t)f2h(hi) << 16);
-  else return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
-}
-
-// byte offset of 16-byte chunk c of row r in a staged image with BK 16-bit elements per row: the
-// chunk index is XORed with the row so that the 16 rows one fragment read touches spread over the
-// banks (two rows per bank group instead of eight or sixteen)
-template <int BK>
-__device__ __forceinline__ int lds_chunk(int r, int c) {
-  constexpr int CPR = BK / 8;
-  const int s = BK == 64 ? (r & 7) : ((r >> 1) & 3);
-  return r * (BK * 2) + ((c ^ s) & (CPR - 1)) * 16;
-}
 
 // F16: f16 tensors (else bf16); BK: channels per K step; NF: 16-channel fragments per wave (BN = 32 NF);
 // PARTIAL: store the f32 partial of this block's K range instead of the rounded tile; FORM: where a tap
@@ -197,39 +164,7 @@ __global__ __launch_bounds__(kConvThreads) void conv3x3_kernel(ConvArgs a) {
     for (int i = 0; i < NB; ++i) *reinterpret_cast<u32x4_t*>(ldsB + b_lds[i]) = rb[i];
   };
 
-  f32x4_t acc[4][NF];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int fr = lane & 15, fq = lane >> 4;
-  load_step(t_begin);
-  write_step();
-  __syncthreads();
-  for (int t = t_begin; t < t_end; ++t) {
-    const bool more = t + 1 < t_end;
-    if (more) load_step(t + 1);
-#pragma unroll
-    for (int kk = 0; kk < BK / 32; ++kk) {
-      u32x4_t fa[4], fb[NF];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        fa[i] = *reinterpret_cast<const u32x4_t*>(ldsA + lds_chunk<BK>(wm * 64 + i * 16 + fr, kk * 4 + fq));
-#pragma unroll
-      for (int j = 0; j < NF; ++j)
-        fb[j] = *reinterpret_cast<const u32x4_t*>(ldsB + lds_chunk<BK>(wn * (16 * NF) + j * 16 + fr, kk * 4 + fq));
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NF; ++j) acc[i][j] = mma16<F16>(fa[i], fb[j], acc[i][j]);
-    }
-    __syncthreads();
-    if (more) {
-      write_step();
-      __syncthreads();
-    }
-  }
+  P2P_MMA_TILE_LOOP(t_begin, t_end)
 
   // acc[i][j][e]: pixel m0 + wm 64 + i 16 + fq 4 + e, channel n0 + wn 16 NF + j 16 + fr
   if constexpr (PARTIAL) {

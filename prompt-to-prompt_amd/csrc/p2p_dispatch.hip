@@ -1,4 +1,4 @@
-// run_self / run_cross / run_conv3x3: pick the kernel form (p2p_select.h) and hand it to its file's launcher.
+// run_self / run_cross / run_conv3x3 / run_linear: pick the kernel form (p2p_select.h) and hand it to its file's launcher.
 // Host code only; nothing here decides.
 #include "p2p_kernels.h"
 
@@ -49,6 +49,28 @@ int run_conv3x3(const p2p_conv3x3_args& a, hipStream_t st) {
   e.n = a.n, e.in_height = a.height, e.in_width = a.width, e.c_in = a.c_in, e.c_out = a.c_out;
   e.dtype = a.dtype, e.form = P2P_CONV_SAME;
   return run_conv3x3_ex(e, st);
+}
+
+int run_linear(const p2p_linear_args& a, hipStream_t st) {
+  if (!a.x || !a.weight || !a.y || (a.form == P2P_LINEAR_RESIDUAL && !a.res)) return P2P_E_ARG;
+  const int rc = linear_check_sizes(a.form, a.m, a.k, a.n);
+  if (rc == P2P_E_ARG) return rc;
+  const bool residual = a.form == P2P_LINEAR_RESIDUAL;
+  // x's and res's element offsets are 32-bit in the kernel too
+  if (a.x_row_stride < 0 || (int64_t)(a.m - 1) * a.x_row_stride + a.k > INT32_MAX) return P2P_E_ARG;
+  if (residual && (a.res_row_stride < 0 || (int64_t)(a.m - 1) * a.res_row_stride + a.n > INT32_MAX)) return P2P_E_ARG;
+  if (a.dtype != P2P_DTYPE_BF16 && a.dtype != P2P_DTYPE_F16) return P2P_E_DTYPE;
+  if (rc < 0) return rc;
+  if (a.x_row_stride % 8 || a.x_row_stride < a.k) return P2P_E_ALIGN;
+  if (residual && (a.res_row_stride % 8 || a.res_row_stride < a.n)) return P2P_E_ALIGN;
+  uintptr_t ptrs = (uintptr_t)a.x | (uintptr_t)a.weight | (uintptr_t)a.y | (uintptr_t)a.workspace;
+  if (residual) ptrs |= (uintptr_t)a.res;
+  if (a.form == P2P_LINEAR_GEGLU) ptrs |= (uintptr_t)a.p_out;
+  if ((ptrs & 15) || ((uintptr_t)a.bias & 1)) return P2P_E_ALIGN;
+  const LinearPlan plan = select_linear(a.form, a.m, a.k, a.n);
+  if (plan.split < 1) return P2P_E_ALIGN;   // a shape the selection leaves to the caller's GEMM
+  if (plan.split > 1 && !a.workspace) return P2P_E_ARG;
+  return launch_linear(a, plan, st);
 }
 
 }  // namespace p2p

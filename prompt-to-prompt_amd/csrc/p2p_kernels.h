@@ -217,6 +217,10 @@ int run_conv3x3(const p2p_conv3x3_args& a, hipStream_t st);   // forwards to run
 int run_conv3x3_ex(const p2p_conv3x3_ex_args& a, hipStream_t st);
 int launch_conv3x3(const p2p_conv3x3_ex_args& a, int out_h, int out_w, const ConvPlan& plan, hipStream_t st);
 int run_conv3x3_pack(const p2p_conv3x3_pack_args& a, hipStream_t st);
+// the feed-forward GEMMs: checks and selection (p2p_dispatch.hip), linear_kernel and its reduce
+// launch (p2p_linear.hip)
+int run_linear(const p2p_linear_args& a, hipStream_t st);
+int launch_linear(const p2p_linear_args& a, const LinearPlan& plan, hipStream_t st);
 // the glue's backward.  From kGnBwdWideRow pixels a channel's row of the NCHW reduce takes a whole
 // workgroup (four waves), below it one wave; token-major dy leaves one partial per 64-pixel tile.
 constexpr int kGnBwdWideRow = 2048;

@@ -462,4 +462,76 @@ inline ConvPlan select_conv3x3(int form, int n, int h, int w, int c_in, int c_ou
   return select_conv3x3(n, h, w, c_in, c_out);
 }
 
+// ---------------------------------------------------------------------------- linear layers
+// linear_kernel (p2p_linear.hip): conv3x3_kernel's tile loop on y = x[m, k] . W[n, k]^T -- 128 rows x
+// bn staged weight rows per workgroup, bk of k per step, `split` workgroups along k per tile (their
+// f32 partials summed in split order by linear_reduce_kernel).  split == 0: the caller's GEMM.
+struct LinearPlan {
+  int bk, bn, split;
+};
+
+// sizes p2p_linear rejects before anything else: 0, or the P2P_E_* code.  n: output columns (the
+// GEGLU form's weight has 2 n rows)
+inline int linear_check_sizes(int form, int m, int k, int n) {
+  if (form != P2P_LINEAR_BIAS && form != P2P_LINEAR_GEGLU && form != P2P_LINEAR_RESIDUAL) return P2P_E_ARG;
+  if (m < 1 || k < 1 || n < 1) return P2P_E_ARG;
+  const int64_t rows = form == P2P_LINEAR_GEGLU ? (int64_t)2 * n : n;
+  // the element offsets into x, the weight, y and p_out are 32-bit in the kernel
+  if ((int64_t)m * k > INT32_MAX || rows * k > INT32_MAX || (int64_t)m * rows > INT32_MAX) return P2P_E_ARG;
+  if (k % 32 || n % 8) return P2P_E_ALIGN;
+  return 0;
+}
+
+// output columns of one tile: the GEGLU form stages a column's h row and its gate row
+inline int linear_tile_cols(int form, const LinearPlan& p) { return form == P2P_LINEAR_GEGLU ? p.bn / 2 : p.bn; }
+
+// Shapes measured slower than the chain they replace stay with the caller's GEMM (tools/linear_bench.py
+// at N = 8, bf16, profiles/r23/linear/linear_bench.txt): the three feed-forward
+// output GEMMs whose K is split -- their f32 partials cost more than the add they save, 54.6 us
+// against 42.8 at 32 x 32 (split 2), 60.1 against 48.8 at 16 x 16 (split 4), 52.5 against 28.4 at
+// 8 x 8 (split 8) -- and the GEGLU GEMM at 8 x 8 (320 tiles: 34.1 against 27.7).  A weight that lost at
+// m rows is declined for every m up to that: fewer rows are fewer tiles still.
+struct LinearDeclined {
+  int form, k, n, max_m;
+};
+constexpr LinearDeclined kLinearDeclined[] = {
+    {P2P_LINEAR_RESIDUAL, 2560, 640, 8192},
+    {P2P_LINEAR_RESIDUAL, 5120, 1280, 2048},
+    {P2P_LINEAR_GEGLU, 1280, 5120, 512},
+};
+inline bool linear_declined(int form, int m, int k, int n) {
+  for (const LinearDeclined& d : kLinearDeclined)
+    if (form == d.form && k == d.k && n == d.n && m <= d.max_m) return true;
+  return false;
+}
+
+// Tile shape and K split from the sizes alone (never the device), by conv3x3_kernel's rules.  bk: 64
+// where it divides k, else 32.  bn: 160 where it divides n and bk is 64, else 128; the GEGLU form
+// always 128 (its fragments pair up: 64 output columns a tile).  split: as many as bring the grid to
+// kConvFillTiles workgroups, at most kConvMaxSplit, never leaving a split fewer than kConvMinSteps
+// steps; the GEGLU form is never split.
+inline LinearPlan select_linear(int form, int m, int k, int n) {
+  LinearPlan p = {0, 0, 0};
+  if (linear_check_sizes(form, m, k, n) != 0 || linear_declined(form, m, k, n)) return p;
+  p.bk = k % 64 == 0 ? 64 : 32;
+  p.bn = (form != P2P_LINEAR_GEGLU && p.bk == 64 && n % 160 == 0) ? 160 : 128;
+  const int cols = linear_tile_cols(form, p);
+  const int64_t tiles = (int64_t)((m + kConvBM - 1) / kConvBM) * ((n + cols - 1) / cols);
+  const int steps = k / p.bk;
+  int64_t s = 1;
+  if (form != P2P_LINEAR_GEGLU && tiles < kConvFillTiles) {
+    s = (kConvFillTiles + tiles - 1) / tiles;
+    if (s > kConvMaxSplit) s = kConvMaxSplit;
+    if (s > steps / kConvMinSteps) s = steps / kConvMinSteps;
+    if (s < 1) s = 1;
+  }
+  p.split = (int)s;
+  return p;
+}
+// f32 elements of p2p_linear_args.workspace: [split][n][m rounded up to the tile]
+inline int64_t linear_workspace_floats(int form, int m, int k, int n) {
+  const LinearPlan p = select_linear(form, m, k, n);
+  return p.split > 1 ? (int64_t)p.split * n * ((m + kConvBM - 1) / kConvBM * kConvBM) : 0;
+}
+
 }  // namespace p2p

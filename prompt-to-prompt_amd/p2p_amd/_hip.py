@@ -189,6 +189,16 @@ class Conv3x3ExArgs(ctypes.Structure):
     ]
 
 
+class LinearArgs(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("res", ctypes.c_void_p),
+        ("y", ctypes.c_void_p), ("p_out", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("x_row_stride", ctypes.c_int64), ("res_row_stride", ctypes.c_int64),
+        ("m", ctypes.c_int32), ("k", ctypes.c_int32), ("n", ctypes.c_int32), ("form", ctypes.c_int32),
+        ("dtype", ctypes.c_int32),
+    ]
+
+
 class Conv3x3PackArgs(ctypes.Structure):
     _fields_ = [
         ("weight", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("c_in", ctypes.c_int32), ("c_out", ctypes.c_int32),
@@ -335,7 +345,8 @@ def lib():
                  "p2p_attn_bwd_workspace": ctypes.c_int64, "p2p_group_norm_stats_floats": ctypes.c_int64,
                  "p2p_group_norm_bwd_workspace_floats": ctypes.c_int64,
                  "p2p_conv3x3_workspace_floats": ctypes.c_int64,
-                 "p2p_conv3x3_ex_workspace_floats": ctypes.c_int64}
+                 "p2p_conv3x3_ex_workspace_floats": ctypes.c_int64,
+                 "p2p_linear_workspace_floats": ctypes.c_int64}
         for fn in EXPORTED_SYMBOLS:
             getattr(L, fn).restype = other.get(fn, ctypes.c_int)
         L.p2p_error_string.argtypes = [ctypes.c_int]
@@ -371,6 +382,9 @@ def lib():
         L.p2p_conv3x3_ex.argtypes = [ctypes.POINTER(Conv3x3ExArgs), vp]
         L.p2p_conv3x3_ex_split.argtypes = [i32, i32, i32, i32, i32, i32]
         L.p2p_conv3x3_ex_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32]
+        L.p2p_linear.argtypes = [ctypes.POINTER(LinearArgs), vp]
+        L.p2p_linear_split.argtypes = [i32, i32, i32, i32]
+        L.p2p_linear_workspace_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_group_norm_bwd.argtypes = [ctypes.POINTER(GroupNormBwdArgs), vp]
         L.p2p_group_norm_bwd_workspace_floats.argtypes = [i32, i32, i32, i32]
         L.p2p_geglu_bwd.argtypes = [ctypes.POINTER(GegluBwdArgs), vp]
@@ -424,7 +438,8 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_conv3x3_pack", "p2p_dpm_step", "p2p_direct_step", "p2p_direct_offset",
                     "p2p_ddpm_step", "p2p_ddpm_noise", "p2p_mutual_attn_fwd", "p2p_mutual_attn_kernel",
                     "p2p_token_classes", "p2p_conv3x3_ex", "p2p_conv3x3_ex_split",
-                    "p2p_conv3x3_ex_workspace_floats")
+                    "p2p_conv3x3_ex_workspace_floats", "p2p_linear", "p2p_linear_split",
+                    "p2p_linear_workspace_floats")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -1315,6 +1330,69 @@ def conv3x3_up2(x_tokens, packed, bias, h: int, w: int):
 def conv3x3_down2(x_tokens, packed, bias, h: int, w: int):
     """conv3x3_ex in the CONV_DOWN2 form: Downsample2D's stride-2 convolution."""
     return conv3x3_ex(x_tokens, packed, bias, h, w, CONV_DOWN2)
+
+
+# -- the feed-forward GEMMs (p2p_linear.hip).  As the glue: None where the library does not serve the
+# operands (CPU, f32, sizes or strides off the kernel's grid, a shape the selection declines)
+LINEAR_BIAS, LINEAR_GEGLU, LINEAR_RESIDUAL = 0, 1, 2
+
+
+def linear_split(form: int, m: int, k: int, n: int) -> int:
+    """Workgroups along K per output tile that p2p_linear takes for x [m, k] and n output columns
+    (p2p_select.h): 1 = one launch, above 1 = the split form, 0 or negative = not served."""
+    return int(lib().p2p_linear_split(form, m, k, n))
+
+
+def _rows(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """t [..., C] as a [rows, C] view with a unit last stride (dense and row-strided inputs), else None."""
+    t2 = t.reshape(-1, t.shape[-1])
+    return t2 if t2.stride(-1) == 1 and t2.data_ptr() == t.data_ptr() else None
+
+
+def linear(x, weight, bias=None, form: int = LINEAR_BIAS, res=None, want_p: bool = False):
+    """epilogue(x . weight^T) for x [..., K] and nn.Linear's weight (p2p_linear), f32 accumulation and one
+    rounding.  LINEAR_BIAS: F.linear(x, weight, bias) [..., N].  LINEAR_GEGLU: weight [2 D, K];
+    h * gelu(gate) [..., D] of F.linear's two halves, and with ``want_p`` the pair (out, p): p [..., 2 D]
+    the rounded F.linear itself.  LINEAR_RESIDUAL: F.linear(x, weight, bias) + res, res [..., N].
+    None where the library does not serve the operands; the caller runs its own lines."""
+    ts = (x, weight) + (() if bias is None else (bias,)) + (() if res is None else (res,))
+    if not all(t.is_cuda and t.dtype == x.dtype for t in ts) or x.dtype not in (torch.bfloat16, torch.float16):
+        return None
+    if form not in (LINEAR_BIAS, LINEAR_GEGLU, LINEAR_RESIDUAL) or (res is None) != (form != LINEAR_RESIDUAL) or \
+            (want_p and form != LINEAR_GEGLU):
+        raise HipError(f"linear: form {form} with res {res is not None}, want_p {want_p}")
+    if weight.dim() != 2 or not weight.is_contiguous() or x.dim() < 1 or x.shape[-1] != weight.shape[1] or \
+            (form == LINEAR_GEGLU and weight.shape[0] % 2):
+        return None
+    K = weight.shape[1]
+    N = weight.shape[0] // 2 if form == LINEAR_GEGLU else weight.shape[0]
+    x2 = _rows(x)
+    r2 = None if res is None else _rows(res)
+    if x2 is None or x2.shape[0] < 1 or (res is not None and (r2 is None or tuple(res.shape) != tuple(x.shape[:-1]) + (N,))):
+        return None
+    M = x2.shape[0]
+    if linear_split(form, M, K, N) < 1:
+        return None
+    a = LinearArgs()
+    a.x, a.weight = x2.data_ptr(), weight.data_ptr()
+    a.x_row_stride = x2.stride(0) if M > 1 else K
+    if bias is not None:
+        a.bias = _vec(bias, x, weight.shape[0]).data_ptr()
+    if r2 is not None:
+        a.res, a.res_row_stride = r2.data_ptr(), (r2.stride(0) if M > 1 else N)
+    y = x.new_empty(x.shape[:-1] + (N,))
+    a.y = y.data_ptr()
+    p = x.new_empty(x.shape[:-1] + (2 * N,)) if want_p else None
+    if p is not None:
+        a.p_out = p.data_ptr()
+    n_ws = int(lib().p2p_linear_workspace_floats(form, M, K, N))
+    if n_ws > 0:
+        ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+        a.workspace = ws.data_ptr()
+    a.m, a.k, a.n, a.form, a.dtype = M, K, N, form, _glue_dtype(x)
+    if not _glue_rc(lib().p2p_linear(ctypes.byref(a), _stream(x.device)), "p2p_linear"):
+        return None
+    return (y, p) if want_p else y
 
 
 def geglu(x):

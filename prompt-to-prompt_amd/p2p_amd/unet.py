@@ -145,12 +145,28 @@ class CrossAttention(nn.Module):
         return self.to_out[1](self.to_out[0](out))
 
 
+# The transformer blocks' feed-forward GEMMs run on linear_kernel (csrc/p2p_linear.hip), GEGLU and the
+# residual add in their epilogues, where p2p_select.h serves the shape (A/B switch, read once: 0 =
+# hipBLASLt's GEMMs with the glue kernels behind them everywhere)
+LINEAR_HIP = os.environ.get("P2P_LINEAR", "1") != "0"
+
+
+def _linear_fused(x, lin: nn.Linear) -> bool:
+    """Whether ``lin`` of x may run on p2p_linear: the switch, and the conditions of the glue with
+    ``lin``'s parameters frozen (the kernel computes no gradient for them)."""
+    return LINEAR_HIP and (fused_glue(x, lin.weight) or fused_glue_grad(x, params=(lin.weight, lin.bias)))
+
+
 class GEGLU(nn.Module):
     def __init__(self, dim_in, dim_out):
         super().__init__()
         self.proj = nn.Linear(dim_in, dim_out * 2)
 
     def forward(self, x):
+        if _linear_fused(x, self.proj):     # the GEMM, the bias and the gating in one launch
+            out = unet_grad.linear_geglu(x, self.proj.weight, self.proj.bias)
+            if out is not None:
+                return out
         p = self.proj(x)
         if fused_glue(p) or fused_glue_grad(p):
             out = (unet_grad if torch.is_grad_enabled() else _hip).geglu(p)
@@ -183,7 +199,8 @@ class BasicTransformerBlock(nn.Module):
     def _forward_fused(self, x, context):
         """Each residual add runs inside the LayerNorm that reads it (p2p_layer_norm: the rounded
         sum is stored by the launch that normalises it); the attention modules are called as in the
-        torch lines.  The last add has no norm behind it and stays torch's.  Under autograd the same
+        torch lines.  The last add has no norm behind it: it runs in the epilogue of the feed-forward's
+        second GEMM (``_ff_residual``), or stays torch's where that keeps its lines.  Under autograd the same
         forward runs (unet_grad.layer_norm), so both modes give the same bits."""
         n1, n2, n3 = self.norm1, self.norm2, self.norm3
         out = unet_grad.layer_norm(x, n1.weight, n1.bias, n1.eps)
@@ -199,7 +216,17 @@ class BasicTransformerBlock(nn.Module):
         if out is None:
             raise _hip.HipError("p2p_layer_norm took norm1 and refused norm3 of the same block")
         h, s = out
-        return self.ff(h) + s
+        return self._ff_residual(h, s)
+
+    def _ff_residual(self, h, s):
+        """ff(h) + s: where p2p_linear serves net[2]'s shape the add runs in that GEMM's epilogue,
+        else exactly the torch lines."""
+        geglu, drop, lin = self.ff.net
+        if not _linear_fused(h, lin):
+            return self.ff(h) + s
+        g = drop(geglu(h))
+        out = unet_grad.linear_residual(g, lin.weight, lin.bias, s)
+        return out if out is not None else lin(g) + s
 
     def forward(self, x, context=None):
         norms = (self.norm1, self.norm2, self.norm3)

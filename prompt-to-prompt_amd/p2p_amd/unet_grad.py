@@ -20,6 +20,10 @@ Downsample2D's convolutions (the kernel's Up2 / Down2 forms on a token-major cop
 no-grad forward's two launches, then torch's input gradient of the convolution and, for Up2, of the
 nearest upsampling.
 
+The feed-forward GEMMs (csrc/p2p_linear.hip) run their forward on p2p_linear: ``_LinearGeglu`` has the
+launch store the rounded pre-activation and feeds it to p2p_geglu_bwd, ``_LinearResidual`` passes dout
+on to the residual; both take the input gradient from a torch matmul against the frozen weight.
+
 The wrappers return None where the forward binding reports the input unsupported, as the bindings
 do; a backward binding that rejects what its forward served raises ``HipError``.
 """
@@ -235,6 +239,77 @@ def geglu(x):
     if x.shape[-1] % 2 or x2.stride(-1) != 1 or x2.data_ptr() != x.data_ptr():
         return None
     return _Geglu.apply(x)
+
+
+class _LinearGeglu(torch.autograd.Function):
+    """GEGLU(F.linear(x, weight, bias)) in one p2p_linear launch, which also stores the rounded
+    pre-activation p for the backward: the bits of the no-grad forward (asking for p does not change
+    them).  Backward: p2p_geglu_bwd at the saved p, then torch's matmul against the frozen weight.
+    Weight and bias get no gradient (fused_glue_grad declines parameters that require one)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        out = _hip.linear(x, weight, bias, _hip.LINEAR_GEGLU, want_p=True)
+        if out is None:
+            raise _hip.HipError(f"linear + geglu under autograd: {tuple(x.shape)} {x.dtype} is not served")
+        ctx.save_for_backward(out[1], weight)
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        p, weight = ctx.saved_tensors
+        return _hip.geglu_bwd(dout.contiguous(), p) @ weight, None, None
+
+
+class _LinearResidual(torch.autograd.Function):
+    """F.linear(x, weight, bias) + res in one p2p_linear launch (with its reduce where K is split): the
+    bits of the no-grad forward.  Backward: dout against the frozen weight, and dout itself for the
+    residual.  Saves the weight only."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, res):
+        out = _hip.linear(x, weight, bias, _hip.LINEAR_RESIDUAL, res=res)
+        if out is None:
+            raise _hip.HipError(f"linear + residual under autograd: {tuple(x.shape)} {x.dtype} is not served")
+        ctx.save_for_backward(weight)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        weight, = ctx.saved_tensors
+        dx = dout @ weight if ctx.needs_input_grad[0] else None
+        return dx, None, None, (dout if ctx.needs_input_grad[3] else None)
+
+
+def _linear_served(form: int, x, weight, res=None) -> bool:
+    """Whether _hip.linear takes these operands, decided before an autograd node is made."""
+    n = weight.shape[0] // 2 if form == _hip.LINEAR_GEGLU else weight.shape[0]
+    if x.shape[-1] != weight.shape[1] or not weight.is_contiguous() or _hip._rows(x) is None:
+        return False
+    if res is not None and (_hip._rows(res) is None or tuple(res.shape) != tuple(x.shape[:-1]) + (n,)):
+        return False
+    m = x.numel() // x.shape[-1]
+    return m > 0 and _hip.linear_split(form, m, weight.shape[1], n) >= 1
+
+
+def linear_geglu(x, weight, bias):
+    """_hip.linear in the GEGLU form, differentiable with respect to x.  None where not served."""
+    if not x.requires_grad:
+        return _hip.linear(x, weight, bias, _hip.LINEAR_GEGLU)
+    if not _linear_served(_hip.LINEAR_GEGLU, x, weight):
+        return None
+    return _LinearGeglu.apply(x, weight, bias)
+
+
+def linear_residual(x, weight, bias, res):
+    """_hip.linear in the RESIDUAL form, differentiable with respect to x and res.  None where not served."""
+    if not (x.requires_grad or res.requires_grad):
+        return _hip.linear(x, weight, bias, _hip.LINEAR_RESIDUAL, res=res)
+    if not _linear_served(_hip.LINEAR_RESIDUAL, x, weight, res):
+        return None
+    return _LinearResidual.apply(x, weight, bias, res)
 
 
 def layer_norm(x, gamma, beta, eps: float, add=None):

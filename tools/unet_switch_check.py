@@ -7,7 +7,7 @@ Two trees, or the two settings of P2P_FUSE_UNET, are compared by comparing their
     python tools/unet_switch_check.py off.npy --compare parent.npy      # prints max |delta|
 --pkg DIR imports p2p_amd from another checkout's prompt-to-prompt_amd directory.
 --vs-f32 prints, instead of writing a file, the distance of that forward to the same model run in
-float32, for the setting of the switches the process was started with (P2P_FUSE_UNET, P2P_CONV)."""
+float32, for the setting of the switches the process was started with (P2P_FUSE_UNET, P2P_CONV, P2P_LINEAR)."""
 import argparse
 import os
 import sys
@@ -51,7 +51,8 @@ def main():
         with torch.no_grad():
             ref = model.float()(x, 501, ctx)["sample"]
         d = (y.float() - ref).abs()
-        print(f"{args.out}: fused glue {getattr(unet, 'FUSE_UNET', None)}, HIP conv3x3 {getattr(unet, 'CONV_HIP', None)}: "
+        print(f"{args.out}: fused glue {getattr(unet, 'FUSE_UNET', None)}, HIP conv3x3 {getattr(unet, 'CONV_HIP', None)}, "
+              f"HIP linear {getattr(unet, 'LINEAR_HIP', None)}: "
               f"against the f32 U-Net max |delta| {d.max().item():.4e}, mean {d.mean().item():.4e}, "
               f"max |ref| {ref.abs().max().item():.3f}")
         return
