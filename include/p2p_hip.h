@@ -666,6 +666,14 @@ int p2p_conv3x3_ex_split(int32_t form, int32_t n, int32_t in_height, int32_t in_
 int64_t p2p_conv3x3_ex_workspace_floats(int32_t form, int32_t n, int32_t in_height, int32_t in_width, int32_t c_in,
                                         int32_t c_out);
 
+/* p2p_conv3x3_set_loop: which tile loop p2p_conv3x3 / p2p_conv3x3_ex launch where the plan is 64
+ * channels a step and 160 output channels a tile (additive to ABI 16; process-wide, for tests and A/B
+ * measurements; never change it while a stream is being captured).  0: the selection's choice per
+ * shape (the default); 1: the register-staged loop everywhere; 2 / 3: the global_load_lds ring on 128 /
+ * 256 pixels per workgroup wherever that tile holds.  The output bits are the same under every value.
+ * Any other value: P2P_E_ARG, nothing changes. */
+int p2p_conv3x3_set_loop(int32_t loop);
+
 /* packed[tap, co, ci] = weight[co, ci, tap / 3, tap % 3]: the K-major image p2p_conv3x3 stages.
  * c_in % 32 and c_out % 32, packed on 16 bytes (else P2P_E_ALIGN). */
 typedef struct {

@@ -545,6 +545,8 @@ int64_t p2p_conv3x3_ex_workspace_floats(int32_t form, int32_t n, int32_t in_heig
   return split > 1 ? (int64_t)split * n * oh * ow * c_out : 0;
 }
 
+int p2p_conv3x3_set_loop(int32_t loop) { return set_conv3x3_loop(loop); }
+
 int p2p_conv3x3_pack(const p2p_conv3x3_pack_args* a, p2p_stream_t stream) {
   if (!a) return P2P_E_ARG;
   return run_conv3x3_pack(*a, (hipStream_t)stream);

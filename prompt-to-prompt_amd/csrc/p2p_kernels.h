@@ -217,6 +217,7 @@ int run_conv3x3(const p2p_conv3x3_args& a, hipStream_t st);   // forwards to run
 int run_conv3x3_ex(const p2p_conv3x3_ex_args& a, hipStream_t st);
 int launch_conv3x3(const p2p_conv3x3_ex_args& a, int out_h, int out_w, const ConvPlan& plan, hipStream_t st);
 int run_conv3x3_pack(const p2p_conv3x3_pack_args& a, hipStream_t st);
+int set_conv3x3_loop(int loop);   // p2p_conv3x3_set_loop: a ConvLoop, or P2P_E_ARG
 // the feed-forward GEMMs: checks and selection (p2p_dispatch.hip), linear_kernel and its reduce
 // launch (p2p_linear.hip)
 int run_linear(const p2p_linear_args& a, hipStream_t st);

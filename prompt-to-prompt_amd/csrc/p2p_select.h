@@ -462,6 +462,44 @@ inline ConvPlan select_conv3x3(int form, int n, int h, int w, int c_in, int c_ou
   return select_conv3x3(n, h, w, c_in, c_out);
 }
 
+// The tile loop of a bk = 64, bn = 160 plan (p2p_conv3x3_set_loop's values): conv3x3_kernel's
+// register-staged loop, or conv3x3_pipe_kernel's global_load_lds ring on 128 or 256 pixels per
+// workgroup.  The plan -- bk, bn, split, the workspace -- is the same under each, and so are the bits.
+enum ConvLoop { CONV_LOOP_AUTO = 0, CONV_LOOP_TILE = 1, CONV_LOOP_PIPE128 = 2, CONV_LOOP_PIPE256 = 3 };
+// stage images in the ring: 36,864 B each at 128 pixels, 53,248 B at 256 (160 KiB of LDS).  Measured
+// (tools/conv_bench.py --loops, profiles/r24/conv_pipe/candidates_*.txt, N = 8, bf16): at 256 pixels 3
+// stages against 2 are equal at 64x64 and 32x32 and 5 to 9 % faster at 16x16 and 8x8; at 128 pixels on
+// the 8x8 maps 3 stages 30.9 / 48.9 us, 4 stages 31.4 / 49.4, 2 stages (two workgroups per CU) 36.6 / 59.2.
+constexpr int kConvPipeDepth128 = 3;
+constexpr int kConvPipeDepth256 = 3;
+constexpr int kConvPipeFill = 256;   // workgroups that give every CU one
+
+constexpr int conv3x3_loop_bm(int loop) { return loop == CONV_LOOP_PIPE256 ? 256 : kConvBM; }
+
+// The loop the selection takes for a form at its OUTPUT map h x w, from the sizes alone; CONV_LOOP_TILE
+// for every plan that is not bk = 64, bn = 160 (the ring is built for that tile only).  The ring on 256
+// pixels wherever its tiles and splits give every CU a workgroup, else on 128.  Measured against the
+// register-staged kernel on the same operands (tools/conv_bench.py --loops, profiles/r24/conv_pipe/
+// candidates_1.txt, candidates_2.txt and conv_bench.txt, all 20 convolution shapes of the U-Net at
+// N = 8): the 17 shapes with 256 workgroups or more take 256 pixels (0.76x to 0.93x of that kernel's
+// time; 128 pixels lost to it on each of them, 1.01x to 1.17x), the three 8x8 shapes (128 workgroups
+// at 256 pixels, 256 at 128) take 128 pixels (0.76x to 0.78x; 256 pixels equal to it or 3 % slower).
+// No shape of the U-Net stays on the register-staged loop.
+inline int select_conv3x3_loop(int form, int n, int h, int w, int c_in, int c_out) {
+  const ConvPlan p = select_conv3x3(form, n, h, w, c_in, c_out);
+  if (p.split < 1 || p.bk != 64 || p.bn != 160) return CONV_LOOP_TILE;
+  const int64_t m = (int64_t)n * h * w;
+  const int64_t wgs = ((m + 255) / 256) * (c_out / p.bn) * p.split;
+  return wgs >= kConvPipeFill ? CONV_LOOP_PIPE256 : CONV_LOOP_PIPE128;
+}
+
+// the loop a launch runs: the forced one (p2p_conv3x3_set_loop) where the plan's tile has it, else
+// the selection's
+inline int conv3x3_loop(int forced, const ConvPlan& p, int form, int n, int h, int w, int c_in, int c_out) {
+  if (p.bk != 64 || p.bn != 160) return CONV_LOOP_TILE;
+  return forced == CONV_LOOP_AUTO ? select_conv3x3_loop(form, n, h, w, c_in, c_out) : forced;
+}
+
 // ---------------------------------------------------------------------------- linear layers
 // linear_kernel (p2p_linear.hip): conv3x3_kernel's tile loop on y = x[m, k] . W[n, k]^T -- 128 rows x
 // bn staged weight rows per workgroup, bk of k per step, `split` workgroups along k per tile (their

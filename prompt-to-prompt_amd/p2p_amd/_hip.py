@@ -382,6 +382,7 @@ def lib():
         L.p2p_conv3x3_ex.argtypes = [ctypes.POINTER(Conv3x3ExArgs), vp]
         L.p2p_conv3x3_ex_split.argtypes = [i32, i32, i32, i32, i32, i32]
         L.p2p_conv3x3_ex_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32]
+        L.p2p_conv3x3_set_loop.argtypes = [i32]
         L.p2p_linear.argtypes = [ctypes.POINTER(LinearArgs), vp]
         L.p2p_linear_split.argtypes = [i32, i32, i32, i32]
         L.p2p_linear_workspace_floats.argtypes = [i32, i32, i32, i32]
@@ -406,6 +407,8 @@ def lib():
         L.p2p_set_launch_events.argtypes = [vp, vp]
         if L.p2p_abi_version() != ABI_VERSION:
             raise HipError(f"libp2p_hip.so ABI {L.p2p_abi_version()} != {ABI_VERSION}")
+        if not CONV_PIPE:
+            L.p2p_conv3x3_set_loop(CONV_LOOP_TILE)
         _lib = L
     return _lib
 
@@ -439,7 +442,7 @@ EXPORTED_SYMBOLS = ("p2p_abi_version", "p2p_source_hash", "p2p_error_string", "p
                     "p2p_ddpm_step", "p2p_ddpm_noise", "p2p_mutual_attn_fwd", "p2p_mutual_attn_kernel",
                     "p2p_token_classes", "p2p_conv3x3_ex", "p2p_conv3x3_ex_split",
                     "p2p_conv3x3_ex_workspace_floats", "p2p_linear", "p2p_linear_split",
-                    "p2p_linear_workspace_floats")
+                    "p2p_linear_workspace_floats", "p2p_conv3x3_set_loop")
 
 
 def clock_probe(out: torch.Tensor, ticks: int = 1000):
@@ -1180,6 +1183,18 @@ def bias_residual(a_nchw, b, bias=None, bias2=None, tokens: bool = False):
 
 
 # -- the resnets' 3x3 convolutions (p2p_conv.hip)
+# p2p_conv3x3_set_loop's values (include/p2p_hip.h)
+CONV_LOOP_AUTO, CONV_LOOP_TILE, CONV_LOOP_PIPE128, CONV_LOOP_PIPE256 = 0, 1, 2, 3
+# A/B switch, read once: P2P_CONV_PIPE=0 keeps every 3x3 convolution on the register-staged loop
+CONV_PIPE = os.environ.get("P2P_CONV_PIPE", "1") != "0"
+
+
+def conv3x3_set_loop(loop: int):
+    """Process-wide: the tile loop p2p_conv3x3 / p2p_conv3x3_ex launch where the plan is bk = 64, bn = 160
+    (CONV_LOOP_*; the bits are the same under each).  For tests and A/B runs; not under graph capture."""
+    _check(lib().p2p_conv3x3_set_loop(int(loop)), "p2p_conv3x3_set_loop")
+
+
 def conv3x3_split(n: int, h: int, w: int, c_in: int, c_out: int) -> int:
     """Workgroups along K per output tile that p2p_conv3x3 takes for these sizes (p2p_select.h): 1 =
     one launch, above 1 = the split form, 0 or negative = the sizes are not served."""

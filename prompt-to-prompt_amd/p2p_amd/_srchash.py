@@ -15,7 +15,8 @@ _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = ("p2p_generic.hip", "p2p_mutual.hip", "p2p_self40.hip", "p2p_selfmaps.hip", "p2p_selfmulti.hip", "p2p_selfsplit.hip",
            "p2p_selfwide.hip", "p2p_conv.hip", "p2p_linear.hip", "p2p_cross.hip", "p2p_bwd.hip", "p2p_latent.hip", "p2p_blend.hip", "p2p_unet.hip", "p2p_text.hip", "p2p_image.hip", "p2p_viz.hip", "p2p_null.hip", "p2p_dispatch.hip", "p2p_capi.hip")
 # what the sources include: the headers, and the two files p2p_generic.hip compiles as one object
-HEADERS = ("p2p_device.h", "p2p_kernels.h", "p2p_select.h", "p2p_blend_mask.h", "p2p_mma_tile.h", "../../include/p2p_hip.h",
+HEADERS = ("p2p_device.h", "p2p_kernels.h", "p2p_select.h", "p2p_blend_mask.h", "p2p_mma_tile.h", "p2p_mma_pipe.h",
+           "../../include/p2p_hip.h",
            "p2p_self.hip", "p2p_cross_entry.hip")
 # every file whose text reaches the compiler or the link line, in a fixed order
 FILES = SOURCES + HEADERS + ("Makefile",)

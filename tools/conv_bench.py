@@ -14,8 +14,16 @@ p2p_conv3x3_ex in the Up2 / Down2 form with the bias.  --repeat R measures every
 spread between the medians of one row is the bar a difference has to clear.  --other-lib runs the
 resnet rows' p2p_conv3x3 on another build of the library too (the parent commit's) in the same call.
 
+--loops 1,2,3 times every served row's kernel alone under each value of p2p_conv3x3_set_loop (1 the
+register-staged loop, 2 / 3 the global_load_lds ring on 128 / 256 pixels) --repeat times, on the
+operands of the row, with microseconds per K step of a workgroup and the fraction of the dense peak;
+--other-lib may be given several times, each as PATH or PATH:LOOP (a build with other ring depths,
+under that switch value), and is then timed beside them on both kinds of row.  --alone skips the
+chains and MIOpen.
+
     python tools/conv_bench.py [--iters 15] [--reps 32] [--dtype bf16|f16] [--n 8] [--repeat 1]
-                               [--other-lib /path/to/libp2p_hip.so] [--only resnet|resample]
+                               [--other-lib /path/to/libp2p_hip.so[:LOOP]]... [--loops 1,2,3] [--alone]
+                               [--only resnet|resample]
 """
 import argparse
 import ctypes
@@ -75,7 +83,9 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     ap.add_argument("--n", type=int, default=8)
     ap.add_argument("--repeat", type=int, default=1)
-    ap.add_argument("--other-lib")
+    ap.add_argument("--other-lib", action="append", default=[])
+    ap.add_argument("--loops", default="")
+    ap.add_argument("--alone", action="store_true")
     ap.add_argument("--only", choices=["resnet", "resample"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -90,12 +100,39 @@ def main():
     print("us per call: [before] NCHW norm + MIOpen conv | MIOpen conv alone || [now] token norm + p2p_conv3x3 | "
           "p2p_conv3x3 alone")
     saved = 0.0
-    other = None
-    if args.other_lib:
-        other = ctypes.CDLL(args.other_lib)
-        other.p2p_conv3x3.argtypes = [ctypes.POINTER(_hip.Conv3x3Args), ctypes.c_void_p]
-        other.p2p_conv3x3_workspace_floats.restype = ctypes.c_int64
-        other.p2p_conv3x3_workspace_floats.argtypes = [ctypes.c_int32] * 5
+    loops = [int(v) for v in args.loops.split(",") if v]
+    others = []   # (label, library)
+    for spec in args.other_lib:
+        path, _, loop = spec.partition(":")
+        lib = ctypes.CDLL(path)
+        lib.p2p_conv3x3.argtypes = [ctypes.POINTER(_hip.Conv3x3Args), ctypes.c_void_p]
+        lib.p2p_conv3x3_ex.argtypes = [ctypes.POINTER(_hip.Conv3x3ExArgs), ctypes.c_void_p]
+        lib.p2p_conv3x3_workspace_floats.restype = ctypes.c_int64
+        lib.p2p_conv3x3_workspace_floats.argtypes = [ctypes.c_int32] * 5
+        lib.p2p_conv3x3_ex_workspace_floats.restype = ctypes.c_int64
+        lib.p2p_conv3x3_ex_workspace_floats.argtypes = [ctypes.c_int32] * 6
+        # (one path is one loaded library however often it is named: the value is set before each timing)
+        others.append((os.path.basename(os.path.dirname(path)) + (f" loop {loop}" if loop else ""), lib, int(loop or 0)))
+    other = others[0][1] if others else None
+
+    def candidates(ours, theirs, gflop, steps):
+        """One line per candidate: this build under each --loops value, then every --other-lib."""
+        rows = []
+        for loop in loops:
+            _hip.conv3x3_set_loop(loop)
+            try:
+                rows.append((f"this build, loop {loop}", [graph_us(ours, *timing) for _ in range(args.repeat)]))
+            finally:
+                _hip.conv3x3_set_loop(0)
+        for label, lib, loop in others:
+            if hasattr(lib, "p2p_conv3x3_set_loop"):
+                assert lib.p2p_conv3x3_set_loop(loop) == 0
+            rows.append((label, [graph_us(lambda i: theirs(i, lib), *timing) for _ in range(args.repeat)]))
+        for label, us in rows:
+            best = min(us)
+            print(f"      {label:28s} " + " ".join(f"{u:7.1f}" for u in us) +
+                  f"   {best / steps:5.2f} us per K step ({steps} steps), {gflop / best * 1e3 / PEAK_TFLOPS * 100:4.1f} % of peak",
+                  flush=True)
     with torch.no_grad():
         for res, cin, cout, count in ([] if args.only == "resample" else SHAPES):
             split = _hip.conv3x3_split(N, res, res, cin, cout)
@@ -120,7 +157,7 @@ def main():
             def ours(i):
                 return _hip.conv3x3(toks[i], packed[i], res, res)
 
-            def theirs(i):   # p2p_conv3x3 of the other build on the same operands
+            def theirs(i, other=other):   # p2p_conv3x3 of the other build on the same operands
                 a = _hip.Conv3x3Args()
                 y = toks[i].new_empty((N, cout, res, res))
                 a.x, a.weight, a.y = toks[i].data_ptr(), packed[i].data_ptr(), y.data_ptr()
@@ -134,9 +171,16 @@ def main():
                 assert rc == 0, rc
                 return y
 
+            timing = (sets, args.reps, args.iters, dev)
+            gflop = 2.0 * N * res * res * 9 * cin * cout / 1e9
+            if args.alone:
+                print(f"  {res:2d}^2 {cin:4d} -> {cout:4d} (x{count:2d}) {gflop:6.1f} GFLOP  split {split}", flush=True)
+                if split >= 1:
+                    candidates(ours, theirs, gflop, 9 * cin // 64 // split)
+                del xs, ws, nchw, toks, packed
+                continue
             variants = [before, miopen] + ([now, ours] if split >= 1 else [])
             us = [graph_us(fn, sets, args.reps, args.iters, dev) for fn in variants]
-            gflop = 2.0 * N * res * res * 9 * cin * cout / 1e9
             line = (f"  {res:2d}^2 {cin:4d} -> {cout:4d} (x{count:2d}) {gflop:6.1f} GFLOP  before {us[0]:7.1f} | {us[1]:7.1f} "
                     f"({gflop / us[1] * 1e3:5.0f} TF)")
             if split >= 1:
@@ -146,14 +190,16 @@ def main():
                 saved += count * (us[0] - us[2])
             else:
                 line += " || not served by the selection"
-            if other is not None and split >= 1:
+            if other is not None and split >= 1 and not loops:
                 pairs = [(graph_us(ours, sets, args.reps, args.iters, dev), graph_us(theirs, sets, args.reps, args.iters, dev))
                          for _ in range(max(2, args.repeat))]
                 line += ("  alone, this build / other build, repeated: " +
                          ", ".join(f"{a:.1f} / {b:.1f}" for a, b in pairs))
             print(line, flush=True)
+            if loops and split >= 1:
+                candidates(ours, theirs, gflop, 9 * cin // 64 // split)
             del xs, ws, nchw, toks, packed
-    if args.only != "resample":
+    if args.only != "resample" and not args.alone:
         print(f"sum over the served convolutions of a U-Net call: {saved / 1e3:.2f} ms less per call")
     if args.only == "resnet":
         return
@@ -186,7 +232,28 @@ def main():
             def ours(i):
                 return _hip.conv3x3_ex(toks[i], packed[i], bs[i], res, res, code)
 
+            def theirs(i, lib):   # p2p_conv3x3_ex of another build on the same operands
+                a = _hip.Conv3x3ExArgs()
+                y = toks[i].new_empty((N, ch, out, out))
+                a.x, a.weight, a.bias, a.y = toks[i].data_ptr(), packed[i].data_ptr(), bs[i].data_ptr(), y.data_ptr()
+                n_ws = lib.p2p_conv3x3_ex_workspace_floats(code, N, res, res, ch, ch)
+                if n_ws:
+                    ws_ = torch.empty(n_ws, dtype=torch.float32, device=dev)
+                    a.workspace = ws_.data_ptr()
+                a.n, a.in_height, a.in_width, a.c_in, a.c_out = N, res, res, ch, ch
+                a.dtype, a.form = _hip._glue_dtype(toks[i]), code
+                rc = lib.p2p_conv3x3_ex(ctypes.byref(a), _hip._stream(dev))
+                assert rc == 0, rc
+                return y
+
+            timing = (sets, args.reps, args.iters, dev)
             gflop = 2.0 * N * out * out * 9 * ch * ch / 1e9
+            if args.alone:
+                print(f"  {form:5s} {res:2d}^2 -> {out:2d}^2 {ch:4d} -> {ch:4d} {gflop:6.1f} GFLOP  split {split}", flush=True)
+                if split >= 1:
+                    candidates(ours, theirs, gflop, 9 * ch // 64 // split)
+                del xs, ws, bs, toks, packed
+                continue
             b_us = [graph_us(before, sets, args.reps, args.iters, dev) for _ in range(args.repeat)]
             line = f"  {form:5s} {res:2d}^2 -> {out:2d}^2 {ch:4d} -> {ch:4d} {gflop:6.1f} GFLOP  before " + \
                 " ".join(f"{u:7.1f}" for u in b_us)
@@ -200,7 +267,11 @@ def main():
             else:
                 line += " || not served by the selection"
             print(line, flush=True)
+            if loops and split >= 1:
+                candidates(ours, theirs, gflop, 9 * ch // 64 // split)
             del xs, ws, bs, toks, packed
+    if args.alone:
+        return
     print(f"sum over the served resampling convolutions of a U-Net call: {gained / 1e3:.3f} ms less per call")
 
 
