@@ -5,7 +5,8 @@ against the same reference and printed beside it.  The shapes are the smallest a
 can go wrong: two images in one 128-pixel tile, M below a tile, h != w, a c_out tail, a K step of
 32, and the two largest K, which must take the split path.  Every call writes into a sentinel-
 padded buffer, runs twice and must repeat its bits.  Then the ResnetBlock2D wiring: capture with
-MIOpen left enabled, the P2P_CONV switch, and the packed-weight cache."""
+MIOpen left enabled, the P2P_CONV switch, and the packed-weight cache.
+Every compiled instantiation at a small shape: tests/kernel_matrix.py (a kernel change extends that table)."""
 import copy
 import ctypes
 import functools

@@ -7,7 +7,8 @@ shapes are the smallest at which this loop can go wrong: a full 256-row tile plu
 four images in one tile, M below any tile, h != w with two column tiles, an odd step count above the
 ring's depth, a K split into ranges of 10 and 11 steps (the ring's prologue and drain meet even and
 odd counts), and the Up2 / Down2 source addressing with a bias.  Every call writes into a sentinel-
-padded buffer, runs twice and must repeat its bits.  Sizes of the Up2 / Down2 cases are the INPUT map."""
+padded buffer, runs twice and must repeat its bits.  Sizes of the Up2 / Down2 cases are the INPUT map.
+Every compiled instantiation at a small shape: tests/kernel_matrix.py (a kernel change extends that table)."""
 import ctypes
 import functools
 

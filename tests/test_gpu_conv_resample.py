@@ -7,7 +7,8 @@ torch's own 16-bit chain is measured against the same reference and printed besi
 the INPUT map.  Every call writes into a sentinel-padded buffer, runs twice and must repeat its bits,
 and the binding's own allocation gives the same bits.  The Same form through the new entry with a
 null bias is bit-equal to p2p_conv3x3.  Then the Upsample2D / Downsample2D wiring: the switches,
-capture with MIOpen left enabled, the packed-weight cache, and autograd with frozen parameters."""
+capture with MIOpen left enabled, the packed-weight cache, and autograd with frozen parameters.
+Every compiled instantiation at a small shape: tests/kernel_matrix.py (a kernel change extends that table)."""
 import copy
 import ctypes
 import functools

@@ -8,7 +8,8 @@ and printed beside the kernel's figure.
 The shapes are the smallest at which each mechanism can go wrong: a partial 128-row tile (M = 136),
 a partial column tile (N = 96 on BN = 128, D = 96 on the GEGLU form's 64-column tiles), BN = 160
 (N = 320), BK = 32 (K = 96) and BK = 64 (K = 64, 320), more than one tile both ways, the K split with
-bias and residual (with and without tails), row-strided x and res, a null bias, p_out."""
+bias and residual (with and without tails), row-strided x and res, a null bias, p_out.
+Every compiled instantiation at a small shape: tests/kernel_matrix.py (a kernel change extends that table)."""
 import pytest
 import torch
 import torch.nn.functional as F
